@@ -10,7 +10,9 @@ configs[3] and the scaling is strong.  A "step" is one pass of the fused HIP ker
 rank's whole shard, already resident in HBM.  Frames counted per clip = VAD frames (98) +
 frames after the endpoint crop (data dependent), the frames the reference computes E/ZCR on.
 
-Beside the metric (not part of ``value``):
+A plain run sets up, warms up, times the K steps, writes the last step's outputs when
+``--dump-outputs DIR`` is given, and prints the line.  ``--full`` adds, beside the metric (not part
+of ``value``):
   * ``window_sweep`` -- configs[2]: 10 000 clips x {rectangular, hamming, hanning};
   * ``allgather`` (N > 1) -- the one exchange step, all per-clip results in one RCCL all-gather;
   * ``knn`` -- configs[4]: exact k=5 self-query over 100 000 15-d vectors, queries sharded;
@@ -18,9 +20,16 @@ Beside the metric (not part of ``value``):
     GPU frames/s beside its own CPU baseline (N = 1);
   * ``configs1`` -- configs[1]: 1 000 clips, one launch (the latency-dominated small batch);
   * ``cpu_baseline`` (N = 1) -- the C restatement of the reference on this box's host cores,
-    on a bounded sample of the same clips, whose outputs are also compared with the GPU's.
+    on a bounded sample of the same clips, whose outputs are also compared with the GPU's;
+  * ``timed_outputs_equal`` -- the last timed step's rows against one eager launch, bitwise; the
+    isolated-launch kernel time and the measured HBM read / copy rates in ``roofline``.
 
-    python bench.py [--gpus N --steps K --warmup W]
+``--dump-outputs DIR`` writes what the last timed step returned (rank 0: its own clips for N = 1,
+every clip's gathered results for N > 1) as DIR/feat.npy (float32 [clips, 15]) and
+DIR/start_end.npy, n_frames.npy, status.npy (float64): the batch is seeded, so two builds run with
+the same arguments are comparable output for output.
+
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 
 Without a launcher (no WORLD_SIZE in the environment) ``--gpus N`` > 1 starts the N ranks itself,
@@ -52,6 +61,11 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the metric: window sweep, configs[0] / [1], KNN, CPU baselines, "
+                         "measured HBM peaks, isolated launches, the timed-outputs check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--clips", type=int, default=100000, help="clips of the whole job (sharded over ranks)")
     ap.add_argument("--frame-length", type=int, default=1102)
     ap.add_argument("--frame-shift", type=int, default=441)
@@ -116,6 +130,27 @@ def timed_launches(fn, n, stream):
         b.record(stream)
     torch.cuda.synchronize()
     return float(np.mean([a.elapsed_time(b) for a, b in ev]))
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_BYTES_PER_CLIP = 15 * 4 + 2 * 8 + 8 + 8 + 8  # feat f32 + start/end, n_frames, status, clip_index f64
+
+
+def dump_outputs(path, rows):
+    """--dump-outputs: the per-clip results of packed rows [clips, 19] (a step's return value) as
+    path/<name>.npy -- feat float32, the integer arrays float64 (exact).  More clips than fit
+    DUMP_MAX_BYTES are cut to a fixed seeded sample, whose indices are clip_index.npy."""
+    from src.distributed import result_views
+    os.makedirs(path, exist_ok=True)
+    n = rows.shape[0]
+    keep = DUMP_MAX_BYTES // DUMP_BYTES_PER_CLIP
+    res = {k: v.cpu().numpy() for k, v in result_views(rows).items() if k != "rows"}
+    if n > keep:
+        idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        res = {k: v[idx] for k, v in res.items()}
+        np.save(os.path.join(path, "clip_index.npy"), idx.astype(np.float64))
+    for k, v in res.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(v, np.float32 if k == "feat" else np.float64))
 
 
 def assemble_result(args, world, ranks_seen, rehearsal, backend_name, C, total_frames, elapsed_x, elapsed_g,
@@ -271,8 +306,10 @@ def main():
     # isolated launches, each bracketed by HIP events: reported beside the timed region's figure;
     # after the host-side syncs above the GPU has idled and its clock ramps back up over the first
     # few launches (round 6 kernel trace: 2.75 -> 2.45 ms), so these read high
-    kern_ms_iso = timed_launches(lambda: fx(pool[0]), max(3, min(K, 10)), stream) if P == 1 else \
-        float(np.mean([timed_launches(lambda: fx(pool[p]), 2, stream) for p in range(P)]))
+    kern_ms_iso = None
+    if args.full:
+        kern_ms_iso = timed_launches(lambda: fx(pool[0]), max(3, min(K, 10)), stream) if P == 1 else \
+            float(np.mean([timed_launches(lambda: fx(pool[p]), 2, stream) for p in range(P)]))
     # the timed steps: captured once into a HIP graph and replayed, so host overhead (ctypes,
     # Python) does not throttle short launches; --no-graph launches each step from Python
     graph = None
@@ -309,8 +346,10 @@ def main():
     my_frames = float(sum(frames[i % P] for i in range(K)))
     # the timed steps checked: the last replayed step's outputs (still in the extractor's buffers)
     # against one eager launch of the same batch into fresh buffers, bit for bit
+    if args.dump_outputs and world == 1:
+        dump_outputs(args.dump_outputs, fx._outputs(C, N)["rows"])
     timed_ok = None
-    if graph is not None:
+    if graph is not None and args.full:
         got = fx._outputs(C, N)["rows"].clone()
         fresh = FeatureExtractor(L, S, args.window, vad, device=dev)
         ref = fresh(pool[(K - 1) % P])["rows"]
@@ -357,10 +396,13 @@ def main():
         torch.cuda.synchronize(dev)
         t0 = time.perf_counter()
         for i in range(K):
-            step(i)
+            gathered = step(i)
         torch.cuda.synchronize(dev)
         dist.barrier()
         elapsed_gs = time.perf_counter() - t0  # serial: each gather waits for its extraction
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, gathered)
+        del gathered
         # pipelined (RCCL, equal blocks: every bench configuration): step i's all-gather runs on a
         # second stream beside step i + 1's extraction; two output buffers (two extractors), and an
         # extraction waits (on the device) for the gather that last read its buffer.  Every step
@@ -400,29 +442,17 @@ def main():
             # the last step's gathered rows hold this rank's block as extracted
             xchk = bool(torch.equal(outs[(K - 1) & 1][rank * C:(rank + 1) * C], last))
             del exts, fx2, outs
-        # the all-gather alone (median of 5), for the record
-        rows = fx(pool[0])["rows"]
-        torch.cuda.synchronize(dev)
-        ts = []
-        for _ in range(5):
-            dist.barrier()
-            g0 = time.perf_counter()
-            gather_rows(rows, args.clips)
-            torch.cuda.synchronize(dev)
-            ts.append(time.perf_counter() - g0)
-        ag = {"ms": round(float(np.median(ts)) * 1e3, 4), "bytes": args.clips * OUT_BYTES_PER_CLIP,
-              "collectives": 1, "backend": backend_name,
-              "what": "every clip's packed 76-B result row (feat, start/end, n_frames, status) as written by "
-                      "the kernel, one %s all_gather_into_tensor, no pack/unpack kernels" % backend_name}
+        if args.full:
+            ag = allgather_leg(args, fx, pool[0], dev, backend_name)
     if world > 1:
-        t = torch.tensor([elapsed_x, elapsed_gs, my_frames, kern_ms, kern_ms_iso,
+        t = torch.tensor([elapsed_x, elapsed_gs, my_frames, kern_ms, -1.0 if kern_ms_iso is None else kern_ms_iso,
                           -1.0 if elapsed_gp is None else elapsed_gp], dtype=torch.float64, device=dev)
         tmax = t.clone()
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         tsum = t.clone()
         dist.all_reduce(tsum, op=dist.ReduceOp.SUM)
         elapsed_x, elapsed_gs, total_frames, kern_ms = tmax[0].item(), tmax[1].item(), tsum[2].item(), tmax[3].item()
-        kern_ms_iso = tmax[4].item()
+        kern_ms_iso = tmax[4].item() if kern_ms_iso is not None else None
         elapsed_gp = tmax[5].item() if elapsed_gp is not None else None
         # value: the faster of the two step loops (both measured here, both in the line)
         elapsed_g = elapsed_gs if elapsed_gp is None else min(elapsed_gs, elapsed_gp)
@@ -437,11 +467,12 @@ def main():
     else:
         total_frames = my_frames
 
-    peaks = measured_peaks(pool[0], dev)
-    sweep = window_sweep(args, fx, pool[0], dev, world, rank) if args.sweep_clips > 0 else None
-    cfg0 = configs0_leg(args, pool[0], dev, world) if args.cfg0 else None
-    cfg1 = configs1_leg(args, fx, pool[0], dev, world) if args.small_clips > 0 else None
-    knn = knn_leg(args, fx, pool[0], dev, world, rank) if args.knn_ref > 0 else None
+    # the legs beside the metric: --full only
+    peaks = measured_peaks(pool[0], dev) if args.full else None
+    sweep = window_sweep(args, fx, pool[0], dev, world, rank) if args.full and args.sweep_clips > 0 else None
+    cfg0 = configs0_leg(args, pool[0], dev, world) if args.full and args.cfg0 else None
+    cfg1 = configs1_leg(args, fx, pool[0], dev, world) if args.full and args.small_clips > 0 else None
+    knn = knn_leg(args, fx, pool[0], dev, world, rank) if args.full and args.knn_ref > 0 else None
 
     result = None
     if rank == 0:
@@ -469,7 +500,7 @@ def main():
             result["window_sweep"] = sweep
         if knn is not None:
             result["knn"] = knn
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             result["cpu_baseline"] = cpu_baseline(fx, pool[0], L, S, args.window, vad, args.cpu_seconds)
             result["cpu_baseline_reference_semantics"] = cpu_baseline_reference_semantics(
                 pool[0], L, S, args.window, vad, args.cpu_seconds * 0.75)
@@ -480,6 +511,26 @@ def main():
     if world > 1:
         dist.destroy_process_group()
     return 0
+
+
+def allgather_leg(args, fx, batch, dev, backend_name):
+    """N > 1: the all-gather of one step's rows alone (median of 5), for the record."""
+    import torch
+    import torch.distributed as dist
+    from src.distributed import gather_rows
+    rows = fx(batch)["rows"]
+    torch.cuda.synchronize(dev)
+    ts = []
+    for _ in range(5):
+        dist.barrier()
+        g0 = time.perf_counter()
+        gather_rows(rows, args.clips)
+        torch.cuda.synchronize(dev)
+        ts.append(time.perf_counter() - g0)
+    return {"ms": round(float(np.median(ts)) * 1e3, 4), "bytes": args.clips * OUT_BYTES_PER_CLIP,
+            "collectives": 1, "backend": backend_name,
+            "what": "every clip's packed 76-B result row (feat, start/end, n_frames, status) as written by "
+                    "the kernel, one %s all_gather_into_tensor, no pack/unpack kernels" % backend_name}
 
 
 def measured_peaks(batch, dev, reps=5):

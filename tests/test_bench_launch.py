@@ -61,6 +61,27 @@ def test_multirank_line_carries_both_values():
     assert r8["exchange_own_block_equal"] is True and "pipelined" in r8["config"]["launch"]
 
 
+def test_full_is_off_by_default_and_dump_writes_float_arrays(tmp_path):
+    """A plain run has ``--full`` off; ``--dump-outputs`` writes a step's packed rows [clips, 19] as
+    float32 / float64 arrays that hold exactly the rows' values."""
+    import numpy as np
+    import torch
+    m = _bench_module()
+    assert m.parse([]).full is False and m.parse([]).dump_outputs is None
+    assert m.parse(["--full", "--dump-outputs", "d"]).full is True
+    rng = np.random.default_rng(3)
+    rows = np.zeros((37, 19), dtype=np.int32)
+    rows[:, :15] = rng.standard_normal((37, 15)).astype(np.float32).view(np.int32)
+    rows[:, 15:] = rng.integers(0, 44100, (37, 4))
+    m.dump_outputs(str(tmp_path), torch.from_numpy(rows))
+    got = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert sorted(got) == ["feat", "n_frames", "start_end", "status"]
+    assert got["feat"].dtype == np.float32 and np.array_equal(got["feat"].view(np.int32), rows[:, :15])
+    for k, want in (("start_end", rows[:, 15:17]), ("n_frames", rows[:, 17]), ("status", rows[:, 18])):
+        assert got[k].dtype == np.float64 and np.array_equal(got[k], want)
+    assert m.DUMP_MAX_BYTES <= 64 << 20
+
+
 def test_committed_pipelined_rehearsal_line():
     """The committed 2-rank rehearsal of both exchange loops (gloo, DSP_BENCH_PIPELINE=1)."""
     p = os.path.join(REPO, "profiles", "r06z_rehearsal_pipelined.json")

@@ -10,7 +10,7 @@ OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
-timeout -k 10 400 python3 $R/bench.py "$@" > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 400 python3 $R/bench.py --full "$@" > $OUT/bench.json 2> $OUT/bench.err
 cat $OUT/bench.json
 H="--no-cpu --sweep-clips 0 --knn-ref 0 --no-cfg0 --small-clips 0"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o kt -- python3 $R/bench.py $H "$@" > $OUT/kt.log 2>&1

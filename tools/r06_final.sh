@@ -25,7 +25,7 @@ if [[ " $S " == *" pmc "* ]]; then
   cat $O/../${T}pmc/pmc.txt $O/../${T}pmc/pmc_busy.txt 2>/dev/null | head -40
 fi
 if [[ " $S " == *" rehearsal "* ]]; then
-  DSP_BENCH_ONE_DEVICE=1 DSP_BENCH_BACKEND=gloo timeout -k 10 400 python3 bench.py --gpus 2 --steps 10 --warmup 2 --sweep-clips 0 --knn-ref 20000 --no-cpu --small-clips 0 --no-cfg0 > $O/rehearsal.json 2> $O/rehearsal.err || { tail -5 $O/rehearsal.err; exit 1; }
+  DSP_BENCH_ONE_DEVICE=1 DSP_BENCH_BACKEND=gloo timeout -k 10 400 python3 bench.py --full --gpus 2 --steps 10 --warmup 2 --sweep-clips 0 --knn-ref 20000 --no-cpu --small-clips 0 --no-cfg0 > $O/rehearsal.json 2> $O/rehearsal.err || { tail -5 $O/rehearsal.err; exit 1; }
   tail -1 $O/rehearsal.json | cut -c1-400
 fi
 if [[ " $S " == *" knn "* ]]; then

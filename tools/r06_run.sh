@@ -9,7 +9,7 @@ if [ "${TESTS:-1}" = 1 ]; then
   [ $rc -eq 0 ] || { grep -E "FAILED|Error|assert" $O/gpu_tests.log | head -30; exit $rc; }
 fi
 if [ "${BENCH:-1}" = 1 ]; then
-  timeout -k 10 900 python -u bench.py ${BENCH_ARGS} > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+  timeout -k 10 900 python -u bench.py --full ${BENCH_ARGS} > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
   tail -c 3000 $O/bench.json
 fi
 if [ "${PROF:-0}" = 1 ]; then
