@@ -2114,6 +2114,13 @@ extern "C" size_t dsp_extract_lds_bytes(int64_t max_len, int frame_length, int f
     return c.total + 4 * EXTRACT_THREADS <= EXTRACT_LDS_LIMIT ? (size_t)c.total : 0;
 }
 
+// diagnostic: the layout dsp_extract_features picks below for these launch arguments
+extern "C" int dsp_extract_fast_layout(int64_t max_len, int frame_length, int frame_shift)
+{
+    if (dsp_extract_lds_bytes(max_len, frame_length, frame_shift) == 0) return 0;
+    return extract_fast_fits((int)max_len, frame_length, frame_shift) ? 1 : 0;
+}
+
 // CU count per device (the persistent grid), cached on first use of each device
 static int g_num_cus[64];
 

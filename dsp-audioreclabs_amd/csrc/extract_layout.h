@@ -82,7 +82,8 @@ __host__ __device__ inline ExtractCarve extract_carve(int ncap, int L, int S)
 
 // The fast kernel's layout is fixed at compile time (every LDS address an immediate) and serves
 // every launch whose clips fit it: the whole clip in registers, <= 128 VAD and feature frames,
-// window rows of <= EXTRACT_FAST_WROW floats (frame_length <= 1256).
+// window rows of <= EXTRACT_FAST_WROW floats (frame_length <= 1260: EXTRACT_WROW(L) rounds
+// L + 2 * EXTRACT_WPAD + 4 up to a multiple of 4, and 1260 + 20 = 1280).
 #define EXTRACT_FAST_NV 128
 #define EXTRACT_FAST_NF 128
 #ifndef EXTRACT_FAST_WROW

@@ -29,7 +29,8 @@ QUEUE_WS_BYTES = 4096  # DSP_QUEUE_WS_BYTES
 OUT_ROW_WORDS = 19  # DSP_OUT_ROW_WORDS: feat[15] (f32), start, end, n_frames, status
 KNN_REF_READY = 1  # DSP_KNN_REF_READY
 
-EXPORTS = ("dsp_extract_lds_bytes", "dsp_extract_features", "dsp_extract_general_workspace_bytes",
+EXPORTS = ("dsp_extract_lds_bytes", "dsp_extract_fast_layout", "dsp_extract_features",
+           "dsp_extract_general_workspace_bytes",
            "dsp_extract_general", "dsp_knn_workspace_bytes", "dsp_knn_workspace_fallbacks_offset",
            "dsp_knn_classify", "dsp_zscore_fit", "dsp_zscore_apply", "dsp_wav_scan", "dsp_wav_read",
            "dsp_abi_version")
@@ -70,6 +71,9 @@ def load_library(path=LIB_PATH):
         raise HipError("%s lacks %s: rebuild it" % (path, ", ".join(missing)))
     L.dsp_extract_lds_bytes.restype = sz
     L.dsp_extract_lds_bytes.argtypes = [i64, i32, i32]
+    if hasattr(L, "dsp_extract_fast_layout"):  # (older A/B variants lack it)
+        L.dsp_extract_fast_layout.restype = i32
+        L.dsp_extract_fast_layout.argtypes = [i64, i32, i32]
     L.dsp_extract_features.restype = i32
     L.dsp_extract_features.argtypes = [vp, vp, i32, i64, i32, i32, vp, i32, dbl, dbl, dbl,
                                        vp, vp, vp, vp, i32, vp, vp, i32, vp, i32, vp, vp]

@@ -67,6 +67,11 @@ extern "C" {
 /* Bytes of dynamic LDS dsp_extract_features needs for clips of up to max_len samples
  * (0 if it exceeds the 160 KiB of one CU). Host-only helper. */
 size_t dsp_extract_lds_bytes(int64_t max_len, int frame_length, int frame_shift);
+/* Diagnostic (host only): 1 when a dsp_extract_features launch with these arguments runs the
+ * kernel with the compile-time LDS layout (the clip in registers; csrc/extract_layout.h
+ * extract_fast_fits), 0 when it runs the runtime carve -- and 0 wherever dsp_extract_lds_bytes
+ * returns 0.  Both layouts compute the same results; tests use it to know which one they reached. */
+int dsp_extract_fast_layout(int64_t max_len, int frame_length, int frame_shift);
 
 /*
  * dsp_extract_features -- fused per-clip pipeline: persistent workgroups (three per CU on the

@@ -51,6 +51,39 @@ def test_lds_sizing(lib):
     assert lib.dsp_extract_lds_bytes(44100, 0, 441) == 0
 
 
+def test_fast_layout_query(lib):
+    """dsp_extract_fast_layout flips exactly where csrc/extract_layout.h (extract_fast_fits) says.
+
+    The compile-time layout holds EXTRACT_THREADS x EXTRACT_RREG = 512 x 3 = 1536 32-sample words
+    including an alignment lead of up to 7 samples, at most 128 VAD and 128 feature frames, and
+    window rows of at most EXTRACT_FAST_WROW = 1280 floats:
+      words  (n + 7 + 31) // 32 <= 1536            <=>  n <= 1536 * 32 - 7 = 49145
+      nvcap  (n - L) // S + 1 <= 128               <=>  n <= L + 128 * S - 1
+      fcap   ceil((n - L) / S) + 1 <= 128          <=>  n <= L + 127 * S
+      WROW   (L + 2 * 8 + 4 + 3) & ~3 <= 1280      <=>  L + 23 <= 1283  <=>  L <= 1260
+    At 1102/441 the frame limits are 1102 + 127 * 441 = 57109 > 49145, so the word count decides:
+    the largest FAST max_len is 49145.  At 882/220 fcap decides: 882 + 127 * 220 = 28822 (128
+    feature frames; the 129th VAD frame would only start at 882 + 128 * 220 = 29042).  The largest
+    FAST frame_length is 1260 (the header's comment used to say 1256)."""
+    q = lib.dsp_extract_fast_layout
+    assert q(44100, 1102, 441) == 1
+    assert q(66150, 1102, 441) == 0
+    nmax = 1536 * 32 - 7
+    assert nmax == 49145 and nmax < 1102 + 127 * 441
+    assert q(nmax, 1102, 441) == 1 and q(nmax + 1, 1102, 441) == 0
+    assert q(882 + 127 * 220, 882, 220) == 1 and q(882 + 127 * 220 + 1, 882, 220) == 0
+    lmax = 1260
+    assert ((lmax + 2 * 8 + 4 + 3) & ~3) == 1280 and ((lmax + 1 + 2 * 8 + 4 + 3) & ~3) > 1280
+    assert q(44100, lmax, 441) == 1 and q(44100, lmax + 1, 441) == 0
+    assert q(1, 1102, 441) == 1 and q(1, lmax + 1, 441) == 0
+    # 0 wherever dsp_extract_lds_bytes is 0
+    for args in ((0, 1102, 441), (44100, 0, 441), (44100, 1102, 0), (400000, 1102, 441)):
+        assert lib.dsp_extract_lds_bytes(*args) == 0 and q(*args) == 0
+    # the generic layout still has an on-chip plan where the compile-time one does not fit
+    assert lib.dsp_extract_lds_bytes(nmax + 1, 1102, 441) > 0
+    assert lib.dsp_extract_lds_bytes(44100, lmax + 1, 441) > 0
+
+
 def test_host_argument_checks(lib):
     """Argument errors are returned before anything touches the device."""
     from src import _hip

@@ -40,32 +40,58 @@ def test_library_and_device():
     _hip.require_device()
 
 
-def test_golden_pipeline(golden, packed):
+def _golden_pipeline(golden, pcm, off, idx, want_fast):
+    """The golden clips `idx` (indices into the golden file), packed in `pcm` at `off` in that
+    order, through every golden configuration; `want_fast` is the fused layout (compile-time 1,
+    runtime carve 0) every launch must take."""
+    from src import _hip
     from src.pipeline import FeatureExtractor
-    pcm, off = packed
     names = golden["clip_names"]
+    max_len = int(np.diff(off).max())
     for key, L, S, wname, vad in golden_keys(golden):
+        assert _hip.lib().dsp_extract_fast_layout(max_len, L, S) == want_fast, (key, max_len)
         fx = FeatureExtractor(L, S, wname, bool(vad), return_vad_lists=True, return_sequences=True)
         out = {k: v.cpu().numpy() for k, v in fx(pcm, off).items()}
         st = out["status"] & 0xFF
-        assert np.array_equal(st, golden[key + "/status"]), key
-        assert np.array_equal(out["n_frames"], golden[key + "/n_frames"]), key
+        assert np.array_equal(st, golden[key + "/status"][idx]), key
+        assert np.array_equal(out["n_frames"], golden[key + "/n_frames"][idx]), key
         if vad:
-            assert np.array_equal(out["start_end"], golden[key + "/start_end"]), (key, out["start_end"])
+            assert np.array_equal(out["start_end"], golden[key + "/start_end"][idx]), (key, out["start_end"])
         fo = golden[key + "/frame_off"]
-        for i in range(len(names)):
+        for j, i in enumerate(idx):
             F = fo[i + 1] - fo[i]
-            seq = out["seq"][i, :F]
+            seq = out["seq"][j, :F]
             np.testing.assert_array_equal(seq[:, 2], golden[key + "/frame_zcr"][fo[i]:fo[i + 1]], err_msg=str((key, names[i])))
             np.testing.assert_allclose(seq[:, 0], golden[key + "/frame_energy"][fo[i]:fo[i + 1]], rtol=1e-5, atol=1e-30, err_msg=str((key, names[i])))
             np.testing.assert_allclose(seq[:, 1], golden[key + "/frame_magnitude"][fo[i]:fo[i + 1]], rtol=1e-5, atol=1e-30, err_msg=str((key, names[i])))
             if vad:
                 vo = golden[key + "/vad_off"]
                 nv = vo[i + 1] - vo[i]
-                np.testing.assert_array_equal(out["vad_zcr"][i, :nv], golden[key + "/vad_zcr"][vo[i]:vo[i + 1]])
-                np.testing.assert_allclose(out["vad_energy"][i, :nv], golden[key + "/vad_energy"][vo[i]:vo[i + 1]], rtol=1e-12, atol=0)
-        bad = feat_close(out["feat"], golden[key + "/feat"])
-        assert not bad.any(), (key, [names[i] for i in np.nonzero(bad.any(1))[0]])
+                np.testing.assert_array_equal(out["vad_zcr"][j, :nv], golden[key + "/vad_zcr"][vo[i]:vo[i + 1]])
+                np.testing.assert_allclose(out["vad_energy"][j, :nv], golden[key + "/vad_energy"][vo[i]:vo[i + 1]], rtol=1e-12, atol=0)
+        bad = feat_close(out["feat"], golden[key + "/feat"][idx])
+        assert not bad.any(), (key, [names[idx[j]] for j in np.nonzero(bad.any(1))[0]])
+
+
+def test_golden_pipeline(golden, packed):
+    """Every golden clip in one launch: long_1p5s (66 150 samples) is past the compile-time layout's
+    1 536 words, so this is the generic layout's run of the goldens."""
+    pcm, off = packed
+    _golden_pipeline(golden, pcm, off, np.arange(len(golden["clip_names"])), want_fast=0)
+
+
+def test_golden_pipeline_fast_layout(golden):
+    """The same goldens without long_1p5s, repacked back to back: every launch takes the
+    compile-time (FAST) layout, the one production batches of 1 s clips run."""
+    import torch
+    names = [str(s) for s in golden["clip_names"]]
+    assert "long_1p5s" in names
+    idx = np.array([i for i, s in enumerate(names) if s != "long_1p5s"])
+    clips = [golden_clip(golden, i) for i in idx]
+    off = np.zeros(len(clips) + 1, np.int64)
+    off[1:] = np.cumsum([c.size for c in clips])
+    pcm = torch.as_tensor(np.concatenate(clips + [np.zeros(8, np.int16)])).cuda()
+    _golden_pipeline(golden, pcm, off, idx, want_fast=1)
 
 
 @pytest.mark.parametrize("L,S,win", [(1102, 441, "hamming"), (1024, 512, "hamming"), (1102, 441, "hanning"),
