@@ -43,8 +43,10 @@
 
 #ifndef DSP_ABL  // the phase-ablation instrument (tools/ablate_build.sh, diagnostic builds only;
 #define DSP_ABL 0 // outputs are wrong): skip 1 = R4 frames, 2 = R5 jobs, 4 = R2 sign bits,
-#endif            // 8 = VAD pass-A partial moments, 64 = p90 selection -- the per-phase VALU budget of
-                  // DESIGN.md §8
+#endif            // 8 = VAD pass-A partial moments, 16 = R2 segment prefixes (zseg_word), 32 = VAD pass-B
+                  // interior sums and sign changes, 64 = p90 selection, 128 = the threshold scan (a fixed
+                  // crop instead), 256 = R5 medians only, 512 = R5 moments only -- the per-phase VALU
+                  // budget of DESIGN.md §4.1 (profiles/valu_by_phase.txt)
 
 namespace dsp {
 
@@ -983,12 +985,12 @@ __device__ __forceinline__ void vad_frames_fast(const Ctx &c, const ClipRef &cur
         const int per = (wi1 - wi0 + 2) >> 1;
         const int ws = wi0 + lh * per, we = min(ws + per - 1, wi1);
 #pragma unroll 4
-        for (int w = ws; w <= we; w++) {
+        for (int w = ws; w <= we && !(DSP_ABL & 32); w++) {
             s1 += c.wS1[w];
             s2 += c.wS2[w];
         }
         // sign changes at pairs [u0, u1 - 1) from R2's segment prefixes (lane 0 of the pair)
-        zc = lh ? 0 : zseg_count(c.posw, c.zw, c.ztot, u0, u1 - 1);
+        zc = (lh || (DSP_ABL & 32)) ? 0 : zseg_count(c.posw, c.zw, c.ztot, u0, u1 - 1);
         // the partial word last: its load (issued before the R2 barrier) lands while the LDS
         // sums above run
         if (pa_w >= 0 && !(DSP_ABL & 8)) partial_moments_fast(qa, pa_e0, pa_e1, cs.kneg, s1, s2);
@@ -1118,6 +1120,57 @@ __device__ __forceinline__ int r4_frames(const ExtractParams &p, const Ctx &c, c
     return F;
 }
 
+// R5 for F <= 32 (the typical crop): four jobs on waves 0..3 instead of r5_fast's six -- two
+// sequences share a wave, one per 32-lane half (E below, M above; ZCR alone in the lower half of its
+// wave).  Wave 0 / 1 the medians (wave_bitonic's 32-key groups: the lower half comes out ascending,
+// the upper one descending), wave 2 / 3 the moments.  Every sum is the one r5_fast forms: the
+// 16-lane row partials by the same DPP tree, then row 0 + row 1 of the half (r5_fast adds two more
+// rows, which hold zeros or the max / min pads at F <= 32), so the 15-d vector keeps its bits
+// (100k clips: 2.317 -> 2.290 ms per step, profiles/valu_diet_ab.txt).
+__device__ __forceinline__ void r5_small(const Ctx &c, int F, float *featb, int wid, int lane)
+{
+    if (wid >= 4 || (DSP_ABL & 2)) return;
+    const int r0 = (F - 1) / 2, r1 = F / 2;
+    const int hl = lane & 31;
+    const bool up = lane >= 32, zjob = wid & 1;
+    const bool in = hl < F && !(zjob && up);
+    float x = 0.f;
+    if (in) x = zjob ? (float)c.fZ[hl] : up ? c.fM[hl] : c.fE[hl];
+    const int q = zjob ? 2 : (up ? 1 : 0);  // the lane's sequence
+    if (wid < 2) {
+        if (DSP_ABL & 256) return;
+        unsigned b[1] = {in ? fkey(x) : ~0u};
+        wave_bitonic<1, unsigned, 32>(b, lane);
+        const float a0 = fkey_value(lane_read(b[0], r0)), a1 = fkey_value(lane_read(b[0], r1));
+        const float u0 = fkey_value(lane_read(b[0], 63 - r0)), u1 = fkey_value(lane_read(b[0], 63 - r1));
+        const float v0 = up ? u0 : a0, v1 = up ? u1 : a1;
+        double med;
+        {
+#pragma clang fp contract(off)
+            med = (F & 1) ? (double)v1 : ((double)v0 + (double)v1) / 2.0;
+        }
+        if (hl == 0 && !(zjob && up)) featb[5 * q + 4] = (float)med;
+    } else {
+        if (DSP_ABL & 512) return;
+        const double Fd = (double)F;
+        const double rs = dpp_row_reduce(in ? (double)x : 0.0, OpAdd());
+        const float rmx = dpp_row_reduce(in ? x : -INFINITY, OpMax()), rmn = dpp_row_reduce(in ? x : INFINITY, OpMin());
+        const double mean_lo = (lane_read(rs, 0) + lane_read(rs, 16)) / Fd, mean_hi = (lane_read(rs, 32) + lane_read(rs, 48)) / Fd;
+        const double d = in ? (double)x - (up ? mean_hi : mean_lo) : 0.0;
+        const double rq = dpp_row_reduce(__builtin_fma(d, d, 0.0), OpAdd());
+        const double qq_lo = lane_read(rq, 0) + lane_read(rq, 16), qq_hi = lane_read(rq, 32) + lane_read(rq, 48);
+        const float mx_lo = OpMax()(lane_read(rmx, 0), lane_read(rmx, 16)), mx_hi = OpMax()(lane_read(rmx, 32), lane_read(rmx, 48));
+        const float mn_lo = OpMin()(lane_read(rmn, 0), lane_read(rmn, 16)), mn_hi = OpMin()(lane_read(rmn, 32), lane_read(rmn, 48));
+        // lanes 0-3: the lower sequence's mean, std, max, min; lanes 4-7: the upper one's
+        if (lane < (zjob ? 4 : 8)) {
+            const bool h = lane >= 4;
+            const int k = lane & 3;
+            const double o = k == 0 ? (h ? mean_hi : mean_lo) : k == 1 ? sqrt((h ? qq_hi : qq_lo) / Fd)
+                             : k == 2 ? (double)(h ? mx_hi : mx_lo) : (double)(h ? mn_hi : mn_lo);
+            featb[5 * (zjob ? 2 : (int)h) + k] = (float)o;
+        }
+    }
+}
 // R5 for F <= 128 (compute_statistics x 3, fe.py:46-62): six jobs on waves 0..5 -- wave q (q < 3)
 // the median of sequence q (E, M, ZCR) by an in-wave bitonic sort, wave 3 + q its mean /
 // population std (fp64 sums) / max / min -- no barrier.  np.median: the middle order statistic
@@ -1126,6 +1179,8 @@ __device__ __forceinline__ void r5_fast(const Ctx &c, int F, float *featb, int w
 {
     const int r0 = (F - 1) / 2, r1 = F / 2;
     for (int job = wid; !(DSP_ABL & 2) && job < 6; job += NWAVE) {
+        if ((DSP_ABL & 256) && job < 3) continue;
+        if ((DSP_ABL & 512) && job >= 3) continue;
         const int q = job % 3;
         auto get = [&](int j) -> float { return q == 0 ? c.fE[j] : q == 1 ? c.fM[j] : (float)c.fZ[j]; };
         const bool in0 = lane < F, in1 = lane + 64 < F;
@@ -1724,7 +1779,7 @@ __device__ __forceinline__ bool clip_fast(const ExtractParams &p, const Ctx &c, 
         if (w < nword) c.posw[w] = P[r];
     }
 #pragma unroll
-    for (int r = 0; r < RREG; r++) zseg_word(c.zw, c.ztot, P[r], r * NT + tid, lane, r * NWAVE + wid);
+    for (int r = 0; r < RREG && !(DSP_ABL & 16); r++) zseg_word(c.zw, c.ztot, P[r], r * NT + tid, lane, r * NWAVE + wid);
     if (tid < 2) c.posw[nword + tid] = 0;
     if (tid == 0) c.zw[RREG * NT] = 0;  // (a range ending at the last register word's end)
     MARK(paissue);
@@ -1759,7 +1814,16 @@ __device__ __forceinline__ bool clip_fast(const ExtractParams &p, const Ctx &c, 
         STAMP(i, 3);
         MARK(scan);
         if (wid == 0) {
-            const int flag = vad_scan<true, true>(p, c, nv, lane);
+            int flag = 0;
+            if (DSP_ABL & 128) {  // ablation only: no scan (a fixed crop of 26 frames, the bench's typical one)
+                if (lane == 0) {
+                    sh->n3 = 0;
+                    sh->n1 = nv / 3;
+                    sh->n6 = min(nv / 3 + 25, nv - 1);
+                }
+            } else {
+                flag = vad_scan<true, true>(p, c, nv, lane);
+            }
             if (lane == 0) sh->exact = cs.Mp > 0.0 ? flag : 0;
         }
     }
@@ -1792,7 +1856,8 @@ __device__ __forceinline__ bool clip_fast(const ExtractParams &p, const Ctx &c, 
 
     // ---- R5: 15-d statistics (compute_statistics x 3, fe.py:46-62) ------------------------
     MARK(R5);
-    r5_fast(c, F, featb, wid, lane);
+    if (const int Fu = uni(F); Fu <= 32) r5_small(c, Fu, featb, wid, lane);
+    else r5_fast(c, Fu, featb, wid, lane);
     if (wid == NWAVE - 1) {
         // idle in R5: the next clip's offsets to LDS, so that the loop top does not wait for a global
         // load (nor, through the in-order vmcnt, for the flushed output stores before it)
@@ -2000,6 +2065,7 @@ void extract_kernel(ExtractParams p)
 #ifdef DSP_STAMPS
         if (threadIdx.x == 0 && p.stamps) p.stamps[(size_t)i * 32 + 21] = blockIdx.x;  // the clip's workgroup
 #endif
+        MARK(looptop);
         const ClipRef cur = (FAST && sh->noff_for == i) ? clip_ref_at(p, sh->noff[0], sh->noff[1]) : clip_ref(p, i);
         if (!cur.ok) {
             __syncthreads();  // everyone has read sh->next (the ok path has barriers in its body)
@@ -2025,6 +2091,7 @@ void extract_kernel(ExtractParams p)
             }
             inflight = !FAST && done;
         }
+        MARK(loopbot);
         __syncthreads();  // LDS summaries are rewritten by the next clip; sh->next published
         STAMP(i, 14);
         const int prev = i;
