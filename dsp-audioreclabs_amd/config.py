@@ -1,4 +1,4 @@
-"""Configuration constants of the reference (config.py:29-70), for drop-in callers.
+"""Configuration constants of the reference (config.py:29-78), for drop-in callers.
 
 Unlike the reference, importing this module has no side effects: RESULTS_DIR is created by the
 experiment runner when it writes, not at import (the reference's config.py:25-26 makedirs).
@@ -44,6 +44,9 @@ MLP_HIDDEN_LAYERS = [64, 64, 32]
 MLP_LEARNING_RATE = 0.005
 MLP_EPOCHS = 1000
 MLP_BATCH_SIZE = 108
+
+# ablation_study.py's learning-rate sweep (config.py:78)
+LEARNING_RATES = [0.0001, 0.0003, 0.0005, 0.001, 0.003, 0.005, 0.008, 0.01, 0.03, 0.05, 0.08]
 
 TEST_SIZE = 0.2
 RANDOM_SEED = 42

@@ -3,7 +3,8 @@
 
     python run.py --data-dir <dir with one sub-directory of WAVs per class> [--experiment all]
 
-'all' (the reference's default) runs the classifier and window comparisons; the reference's
+'all' (the reference's default) runs the classifier and window comparisons, with the reference's
+'MLP' row (the fused on-device trainer, src/models.MLPTrainer) when --with-mlp is given; the reference's
 'feature' and 'visualize' experiments only draw plots (src/visualization.py, out of scope) and are
 accepted and reported as such.
 """
@@ -24,6 +25,8 @@ def main(argv=None):
     # frame sizes in samples (config.FRAME_LENGTH / FRAME_SHIFT; BASELINE configs[0]: 1024 / 512)
     ap.add_argument('--frame-length', type=int, default=None, help='frame length in samples')
     ap.add_argument('--frame-shift', type=int, default=None, help='frame shift in samples')
+    ap.add_argument('--with-mlp', action='store_true',
+                    help="add the reference's MLP row (config.MLP_*) to both comparisons")
     args = ap.parse_args(argv)
     if args.data_dir:
         os.environ['SPEECH_DATA_DIR'] = os.path.abspath(os.path.expanduser(args.data_dir))
@@ -57,10 +60,10 @@ def _run(args, config, SpeechRecognitionExperiment):
     last_experiment = exp  # the last run's data (X, y), for callers that drive main() in process
     out = {'frame_length': config.FRAME_LENGTH, 'frame_shift': config.FRAME_SHIFT}
     if args.experiment in ('all', 'classifier'):
-        res = exp.experiment_classifier_comparison(window_type=args.window_type)
+        res = exp.experiment_classifier_comparison(window_type=args.window_type, with_mlp=args.with_mlp)
         out['classifier'] = {k: float(v['accuracy']) for k, v in res.items()}
     if args.experiment in ('all', 'window'):
-        res = exp.experiment_window_comparison()
+        res = exp.experiment_window_comparison(with_mlp=args.with_mlp)
         out['window'] = {w: {c: float(r['accuracy']) for c, r in rw.items()} for w, rw in res.items()}
     if args.experiment in ('feature', 'visualize'):
         print("experiment '%s' draws plots only (src/visualization.py): not part of the accelerated path"

@@ -33,7 +33,8 @@ EXPORTS = ("dsp_extract_lds_bytes", "dsp_extract_fast_layout", "dsp_extract_feat
            "dsp_extract_general_workspace_bytes",
            "dsp_extract_general", "dsp_knn_workspace_bytes", "dsp_knn_workspace_fallbacks_offset",
            "dsp_knn_classify", "dsp_zscore_fit", "dsp_zscore_apply", "dsp_wav_scan", "dsp_wav_read",
-           "dsp_abi_version")
+           "dsp_abi_version", "dsp_mlp_lds_bytes", "dsp_mlp_param_count", "dsp_mlp_train",
+           "dsp_mlp_predict", "dsp_mlp_dropout_mask")
 DSP_WAV_OTHER, DSP_WAV_S16_MONO, DSP_WAV_U8_MONO = 0, 1, 2
 
 _lib = None
@@ -98,6 +99,19 @@ def load_library(path=LIB_PATH):
         L.dsp_wav_scan.argtypes = [vp, i64, i32, vp, vp, vp]
         L.dsp_wav_read.restype = i32
         L.dsp_wav_read.argtypes = [vp, i64, i32, vp, vp, vp, vp, vp]
+    if hasattr(L, "dsp_mlp_train"):  # (older A/B variants lack the MLP)
+        u32, f32 = ctypes.c_uint32, ctypes.c_float
+        L.dsp_mlp_lds_bytes.restype = sz
+        L.dsp_mlp_lds_bytes.argtypes = [i32, i32, vp, i32, i32]
+        L.dsp_mlp_param_count.restype = i64
+        L.dsp_mlp_param_count.argtypes = [i32, i32, vp, i32]
+        L.dsp_mlp_train.restype = i32
+        L.dsp_mlp_train.argtypes = [vp, vp, i64, i64, i64, i32, i32, vp, i32, i32, i32, i32, vp, i64, vp, vp, vp, vp,
+                                    vp, vp, u32, f32, vp, vp, vp]
+        L.dsp_mlp_predict.restype = i32
+        L.dsp_mlp_predict.argtypes = [vp, vp, i64, i32, i32, vp, i32, vp, vp, vp]
+        L.dsp_mlp_dropout_mask.restype = i32
+        L.dsp_mlp_dropout_mask.argtypes = [u32, i64, i32, i32, i32, u32, vp, vp]
     _lib = L
     return L
 

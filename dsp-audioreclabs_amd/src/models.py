@@ -6,7 +6,13 @@ majority vote as scikit-learn's KNeighborsClassifier(n_neighbors=k) (kd_tree, Eu
 uniform weights, scipy.stats.mode: smallest label on ties).  The other classifier types of the
 reference (naive_bayes, decision_tree, svm) are not part of the accelerated path (SURVEY.md §8,
 DESIGN.md §7); they keep the reference's scikit-learn models so a caller switching over loses
-nothing.  The reference's MLP (models.py:77-221, PyTorch training) is out of scope.
+nothing.
+
+``MLPTrainer`` (models.py:109-221) trains the reference's MLP with the fused on-device trainer
+(csrc/mlp.hip: dsp_mlp_train / dsp_mlp_predict) -- the whole serial SGD loop of
+models.py:146-194 in one persistent workgroup, many epochs per launch -- or, outside that kernel's
+plan, with the reference's own loop in plain torch on the device.  ``fit_mlp_models`` trains a
+learning-rate sweep in one launch.
 """
 import numpy as np
 
@@ -71,10 +77,279 @@ class TraditionalClassifier:
         }
 
 
+# ==================== MLP (models.py:77-221) ====================
+
+def _build_network(input_size, hidden_layers, num_classes, dropout):
+    """MLPClassifier.network (models.py:90-103): Linear / ReLU / Dropout per hidden layer, a last Linear."""
+    from torch import nn
+    layers, prev = [], int(input_size)
+    for h in hidden_layers:
+        layers += [nn.Linear(prev, int(h)), nn.ReLU(), nn.Dropout(dropout)]
+        prev = int(h)
+    layers.append(nn.Linear(prev, int(num_classes)))
+    return nn.Sequential(*layers)
+
+
+def _pack(network):
+    """The packed buffer of include/dsp_audiorec.h: the state_dict's tensors in order, flattened."""
+    import torch
+    return torch.cat([t.detach().reshape(-1).to(torch.float32) for t in network.state_dict().values()])
+
+
+def _unpack(network, packed):
+    import torch
+    sd, off = network.state_dict(), 0
+    with torch.no_grad():
+        for t in sd.values():
+            t.copy_(packed[off:off + t.numel()].reshape(t.shape))
+            off += t.numel()
+    return network
+
+
+class MLPTrainer:
+    """models.py:109-221: fit / predict / evaluate, train_losses / train_accuracies, the reference's
+    result keys.  The initial weights are nn.Linear's default init of the reference's module.
+
+    Extensions (keywords after ``device``; the reference has none of them):
+      seed     None: weights from torch's global RNG as in the reference, and a seed for the shuffle
+               and the dropout drawn from it.  An int makes init, shuffle and dropout reproducible
+               without touching the global RNG.
+      dropout  the reference's fixed 0.3 (MLPClassifier's default).
+      backend  'fused': csrc/mlp.hip, the whole training loop in one persistent workgroup
+               (dsp_mlp_train) and dsp_mlp_predict; raises outside its plan (dsp_mlp_lds_bytes == 0).
+               'torch': the reference's loop in plain torch on the ROCm device (any shape; also
+               the baseline of tools/mlp_bench.py).  'auto': fused inside its plan, torch outside.
+    No CPU path: ``fit`` raises HipError without a HIP device (constructing needs none).
+    """
+
+    EPOCH_CHUNK_BYTES = 64 << 20  # bound on one launch's shuffle orders (perm int32 [epochs, N])
+
+    def __init__(self, input_size, hidden_layers, num_classes, learning_rate=0.001, epochs=100, batch_size=16,
+                 device=None, seed=None, dropout=0.3, backend='auto'):
+        import torch
+        if backend not in ('auto', 'fused', 'torch'):
+            raise ValueError("backend must be 'auto', 'fused' or 'torch'")
+        self.input_size, self.hidden_layers = int(input_size), [int(h) for h in hidden_layers]
+        self.num_classes, self.learning_rate = int(num_classes), float(learning_rate)
+        self.epochs, self.batch_size = int(epochs), int(batch_size)
+        self.device, self.dropout, self.backend = device, float(dropout), backend
+        if seed is None:
+            network = _build_network(input_size, self.hidden_layers, num_classes, self.dropout)
+            self.seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
+        else:
+            self.seed = int(seed)
+            with torch.random.fork_rng(devices=[]):
+                torch.manual_seed(self.seed)
+                network = _build_network(input_size, self.hidden_layers, num_classes, self.dropout)
+        self._network = network      # 'torch' backend: the live module (moved to the device at fit)
+        self._params = _pack(network)  # 'fused' backend: packed parameters (on the device after fit)
+        self._m = self._v = self._optimizer = self._gen = None
+        self._steps = 0
+        self._pending = []
+        self._fused = None  # decided at the first fit
+        self.train_losses = []
+        self.train_accuracies = []
+
+    # -- backend choice ---------------------------------------------------------------------
+    def _use_fused(self):
+        if self._fused is None:
+            from .pipeline import mlp_lds_bytes
+            inside = self.backend != 'torch' and mlp_lds_bytes(self.input_size, self.hidden_layers,
+                                                               self.num_classes, self.batch_size) > 0
+            if self.backend == 'fused' and not inside:
+                raise ValueError("MLP shape outside the fused kernel's plan (dsp_mlp_lds_bytes == 0): "
+                                 "use backend='torch' or 'auto'")
+            self._fused = inside
+        return self._fused
+
+    def _device(self):
+        from . import _hip
+        d = _hip.require_device()
+        if self.device is not None:
+            import torch
+            d = torch.device(self.device)
+            if d.type != 'cuda':
+                raise _hip.HipError("the MLP trains only on a HIP device, not on %s" % d)
+        return d
+
+    def _generator(self, d):
+        import torch
+        if self._gen is None:
+            self._gen = torch.Generator(device=d)
+            self._gen.manual_seed(self.seed)
+        return self._gen
+
+    @property
+    def model(self):
+        """The equivalent nn.Sequential (Linear/ReLU/Dropout ... Linear) with the current weights."""
+        if self._fused:
+            net = _build_network(self.input_size, self.hidden_layers, self.num_classes, self.dropout)
+            return _unpack(net, self._params).to(self._params.device).eval()  # a snapshot
+        return self._network
+
+    # -- training ---------------------------------------------------------------------------
+    def fit(self, X_train, y_train, verbose=True):
+        d = self._device()
+        if self._use_fused():
+            _fit_fused([self], X_train, y_train, d, verbose)
+        else:
+            self._fit_torch(X_train, y_train, d, verbose)
+        return self
+
+    def _log(self, first, verbose):
+        if verbose:
+            for e in range(first, len(self.train_losses)):
+                if (e + 1) % 10 == 0:
+                    print(f'Epoch [{e + 1}/{self.epochs}], Loss: {self.train_losses[e]:.4f}, '
+                          f'Accuracy: {self.train_accuracies[e]:.4f}')
+
+    def _flush(self, verbose):
+        """Histories of finished launches (device tensors until here) into the Python lists."""
+        first = len(self.train_losses)
+        for loss, acc in self._pending:
+            self.train_losses += [float(x) for x in loss.cpu().tolist()]
+            self.train_accuracies += [float(x) for x in acc.cpu().tolist()]
+        self._pending = []
+        self._log(first, verbose)
+
+    def _fit_torch(self, X_train, y_train, d, verbose):
+        """models.py:146-194 as written, on the device: one optimizer step per batch, one
+        loss.item() per step.  The shuffle is this trainer's generator, the dropout the device's."""
+        import torch
+        from torch import nn, optim
+        X = torch.as_tensor(np.asarray(X_train), dtype=torch.float32).to(d)
+        y = torch.as_tensor(np.asarray(y_train), dtype=torch.int64).to(d)
+        net = self._network.to(d)
+        if self._optimizer is None:
+            self._optimizer = optim.Adam(net.parameters(), lr=self.learning_rate)
+        criterion, gen, N = nn.CrossEntropyLoss(), self._generator(d), X.shape[0]
+        with torch.random.fork_rng(devices=[d]):
+            torch.manual_seed(self.seed + self._steps)
+            net.train()
+            for _ in range(self.epochs):
+                order = torch.randperm(N, generator=gen, device=d)
+                epoch_loss, correct, total, nb = 0.0, 0, 0, 0
+                for lo in range(0, N, self.batch_size):
+                    idx = order[lo:lo + self.batch_size]
+                    batch_X, batch_y = X[idx], y[idx]
+                    outputs = net(batch_X)
+                    loss = criterion(outputs, batch_y)
+                    self._optimizer.zero_grad()
+                    loss.backward()
+                    self._optimizer.step()
+                    epoch_loss += loss.item()
+                    _, predicted = torch.max(outputs.data, 1)
+                    total += batch_y.size(0)
+                    correct += (predicted == batch_y).sum().item()
+                    nb += 1
+                    self._steps += 1
+                self.train_losses.append(epoch_loss / nb)
+                self.train_accuracies.append(correct / total)
+                self._log(len(self.train_losses) - 1, verbose)
+
+    def predict(self, X_test):
+        import torch
+        if self._fused:
+            from .pipeline import mlp_predict
+            pred, _ = mlp_predict(self._params, np.asarray(X_test, dtype=np.float32), self.hidden_layers,
+                                  self.num_classes)
+            return pred.cpu().numpy().astype(np.int64)
+        d = self._device()
+        net = self._network.to(d)
+        net.eval()
+        with torch.no_grad():
+            outputs = net(torch.as_tensor(np.asarray(X_test), dtype=torch.float32).to(d))
+            _, predicted = torch.max(outputs.data, 1)
+        return predicted.cpu().numpy()
+
+    def evaluate(self, X_test, y_test):
+        from sklearn.metrics import accuracy_score, classification_report, confusion_matrix
+        y_pred = self.predict(X_test)
+        return {
+            'accuracy': accuracy_score(y_test, y_pred),
+            'predictions': y_pred,
+            'classification_report': classification_report(y_test, y_pred, output_dict=True, zero_division=0),
+            'confusion_matrix': confusion_matrix(y_test, y_pred),
+            'train_losses': self.train_losses,
+            'train_accuracies': self.train_accuracies,
+        }
+
+
+def _fit_fused(trainers, X_train, y_train, d, verbose):
+    """The trainers' epochs in launches of dsp_mlp_train, one workgroup per trainer.  Every trainer
+    keeps its own shuffle generator, so a model trains the same alone or in a batch."""
+    import torch
+    from .pipeline import mlp_train
+    t0 = trainers[0]
+    # a list of arrays: one training set per trainer, all of the same shape (else one shared set)
+    X = torch.as_tensor(np.asarray(X_train), dtype=torch.float32).to(d).contiguous()
+    y = torch.as_tensor(np.asarray(y_train)).to(device=d, dtype=torch.int32).contiguous()
+    N, K = X.shape[-2], len(trainers)
+    if X.shape[-1] != t0.input_size or X.dim() != (3 if isinstance(X_train, (list, tuple)) else 2):
+        raise ValueError("X of shape %s does not fit %d models of %d features" % (tuple(X.shape), K, t0.input_size))
+    P = t0._params.numel()
+    params = torch.stack([t._params.to(d) for t in trainers]).contiguous()
+    zeros = torch.zeros(P, dtype=torch.float32, device=d)
+    m = torch.stack([zeros if t._m is None else t._m for t in trainers]).contiguous()
+    v = torch.stack([zeros if t._v is None else t._v for t in trainers]).contiguous()
+    steps = torch.tensor([t._steps for t in trainers], dtype=torch.int64, device=d)
+    lr = torch.tensor([t.learning_rate for t in trainers], dtype=torch.float64, device=d)
+    seeds = torch.as_tensor(np.array([t.seed & 0xFFFFFFFF for t in trainers], dtype=np.uint32).view(np.int32)).to(d)
+    gens = [t._generator(d) for t in trainers]
+    chunk = max(1, min(t0.epochs, MLPTrainer.EPOCH_CHUNK_BYTES // (4 * N * K)))
+    if verbose:
+        chunk = min(chunk, 10)  # the reference's every-10-epochs line appears as training goes
+    done = 0
+    while done < t0.epochs:
+        ne = min(chunk, t0.epochs - done)
+        perm = torch.stack([torch.stack([torch.randperm(N, generator=g, device=d, dtype=torch.int32)
+                                         for _ in range(ne)]) for g in gens]).contiguous()
+        loss, acc = mlp_train(X, y, t0.hidden_layers, t0.num_classes, perm, params, m, v, steps, lr, seeds,
+                              t0.batch_size, dropout=t0.dropout, perm_stride=ne * N if K > 1 else 0)
+        if verbose:
+            loss, acc = loss.cpu(), acc.cpu()
+        for k, t in enumerate(trainers):
+            t._pending.append((loss[k], acc[k]))
+            if verbose:
+                t._flush(K == 1)
+        done += ne
+    nb = (N + t0.batch_size - 1) // t0.batch_size
+    for k, t in enumerate(trainers):
+        t._params, t._m, t._v = params[k].clone(), m[k].clone(), v[k].clone()
+        t._steps += t0.epochs * nb
+        t._flush(False)
+
+
+def fit_mlp_models(X_train, y_train, input_size, hidden_layers, num_classes, learning_rates, seeds=None,
+                   epochs=100, batch_size=16, dropout=0.3, verbose=False):
+    """Train one MLP per learning rate (and seed) in ONE dsp_mlp_train launch per epoch chunk -- a
+    workgroup per model -- and return the fitted MLPTrainers.  Model k equals
+    ``MLPTrainer(..., learning_rate=learning_rates[k], seed=seeds[k], backend='fused').fit(X, y)``
+    bit for bit.  (Extension: the reference trains such sweeps one model after another.)"""
+    from . import _hip
+    seeds = list(range(len(learning_rates))) if seeds is None else list(seeds)
+    if len(seeds) != len(learning_rates):
+        raise ValueError("one seed per learning rate")
+    trainers = [MLPTrainer(input_size, hidden_layers, num_classes, learning_rate=lr, epochs=epochs,
+                           batch_size=batch_size, seed=s, dropout=dropout, backend='fused')
+                for lr, s in zip(learning_rates, seeds)]
+    if not trainers:
+        return trainers
+    d = _hip.require_device()
+    for t in trainers:
+        t._use_fused()
+    _fit_fused(trainers, X_train, y_train, d, verbose)
+    return trainers
+
+
 def create_classifier(classifier_type, **kwargs):
-    """models.py:226-246."""
+    """models.py:226-246.  'mlp' takes MLPTrainer's arguments.  A bare ``create_classifier('mlp')``
+    raises NotImplementedError naming them (the reference fails there with a TypeError)."""
     if classifier_type in ['knn', 'naive_bayes', 'decision_tree', 'svm']:
         return TraditionalClassifier(classifier_type, **kwargs)
     if classifier_type == 'mlp':
-        raise NotImplementedError("the MLP classifier (models.py:77-221) is outside the accelerated path")
+        if not kwargs:
+            raise NotImplementedError("create_classifier('mlp') needs input_size, hidden_layers and num_classes "
+                                      "(MLPTrainer's required arguments, models.py:112-114)")
+        return MLPTrainer(**kwargs)
     raise ValueError(f"不支持的分类器类型: {classifier_type}")

@@ -275,3 +275,99 @@ def zscore_apply(X, mean, std):
     _hip.check(_hip.lib().dsp_zscore_apply(_hip.ptr(X), N, D, _hip.ptr(mean), _hip.ptr(std), _hip.ptr(out),
                                            _hip.stream_handle(d)), "dsp_zscore_apply")
     return out
+
+
+# ---- MLP classifier (csrc/mlp.hip; models.MLPTrainer is the reference-shaped surface) ---------
+
+def _int_array(values):
+    import ctypes
+    values = [int(v) for v in values]
+    return (ctypes.c_int * max(len(values), 1))(*values), len(values)
+
+
+def mlp_param_count(input_size, hidden_layers, num_classes):
+    """Length of the packed nn.Linear parameter buffer (weight [out, in], bias [out], per layer)."""
+    prev, n = int(input_size), 0
+    for h in list(hidden_layers) + [num_classes]:
+        n += prev * int(h) + int(h)
+        prev = int(h)
+    return n
+
+
+def mlp_lds_bytes(input_size, hidden_layers, num_classes, batch_size):
+    """dsp_mlp_lds_bytes: LDS of the fused trainer, 0 when the shape is outside its plan.  Needs the
+    built library, not a GPU."""
+    arr, n = _int_array(hidden_layers)
+    return int(_hip.lib().dsp_mlp_lds_bytes(int(input_size), n, arr, int(num_classes), int(batch_size)))
+
+
+def mlp_drop_threshold(p):
+    """(drop_threshold uint32, keep_scale float32 value) of dropout probability p (include/dsp_audiorec.h)."""
+    if not p:
+        return 0, 1.0
+    return min(int(float(p) * 4294967296.0), 4294967295), float(np.float32(1.0 / (1.0 - float(p))))
+
+
+def mlp_train(X, y, hidden_layers, num_classes, perm, params, m, v, steps, lr, seeds, batch_size,
+              dropout=0.3, perm_stride=0):
+    """dsp_mlp_train on device tensors: X float32 [N, D], y int32 [N] (or one set per model: [n_models,
+    N, D] and [n_models, N]), perm int32 [n_epochs, N] (or
+    [n_models, n_epochs, N] with perm_stride = n_epochs * N), params / m / v float32 [n_models, P],
+    steps int64 [n_models], lr float64 [n_models], seeds int32 [n_models] (the uint32 seeds' bit
+    patterns).  Updates params, m, v, steps in place; returns (loss_hist, acc_hist) float32
+    [n_models, n_epochs] on the device.  Stream-ordered, no host sync."""
+    import torch
+    d = X.device
+    N, D = X.shape[-2:]
+    n_models = params.shape[0]
+    x_stride = N * D if X.dim() == 3 else 0
+    y_stride = N if y.dim() == 2 else 0
+    assert X.dim() == 2 or X.shape[0] == n_models
+    assert y.shape[-1] == N and y.is_contiguous() and (y.dim() == 1 or y.shape[0] == n_models)
+    n_epochs = perm.shape[-2]
+    assert perm.shape[-1] == N and perm.dtype == torch.int32 and perm.is_contiguous()
+    assert X.dtype == torch.float32 and y.dtype == torch.int32 and X.is_contiguous()
+    for t in (params, m, v):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == params.shape
+    assert steps.dtype == torch.int64 and lr.dtype == torch.float64 and seeds.dtype == torch.int32
+    assert steps.numel() == n_models and lr.numel() == n_models and seeds.numel() == n_models
+    assert params.shape[1] == mlp_param_count(D, hidden_layers, num_classes)
+    loss = torch.empty((n_models, n_epochs), dtype=torch.float32, device=d)
+    acc = torch.empty((n_models, n_epochs), dtype=torch.float32, device=d)
+    arr, nh = _int_array(hidden_layers)
+    thr, scale = mlp_drop_threshold(dropout)
+    rc = _hip.lib().dsp_mlp_train(_hip.ptr(X), _hip.ptr(y), N, x_stride, y_stride, D, nh, arr, int(num_classes), n_models, n_epochs,
+                                  int(batch_size), _hip.ptr(perm), int(perm_stride), _hip.ptr(params), _hip.ptr(m),
+                                  _hip.ptr(v), _hip.ptr(steps), _hip.ptr(lr), _hip.ptr(seeds), thr, scale,
+                                  _hip.ptr(loss), _hip.ptr(acc), _hip.stream_handle(d))
+    _hip.check(rc, "dsp_mlp_train")
+    return loss, acc
+
+
+def mlp_predict(params, X, hidden_layers, num_classes, with_logits=False):
+    """dsp_mlp_predict: (pred int32 [Nq], logits float32 [Nq, C] or None) of one packed model."""
+    import torch
+    d = _hip.require_device()
+    X = _as_device(X, torch.float32, d)
+    params = _as_device(params, torch.float32, d).reshape(-1)
+    Nq, D = X.shape
+    assert params.numel() == mlp_param_count(D, hidden_layers, num_classes)
+    pred = torch.empty(Nq, dtype=torch.int32, device=d)
+    logits = torch.empty((Nq, int(num_classes)), dtype=torch.float32, device=d) if with_logits else None
+    arr, nh = _int_array(hidden_layers)
+    rc = _hip.lib().dsp_mlp_predict(_hip.ptr(params), _hip.ptr(X), Nq, D, nh, arr, int(num_classes), _hip.ptr(pred),
+                                    _hip.ptr(logits), _hip.stream_handle(d))
+    _hip.check(rc, "dsp_mlp_predict")
+    return pred, logits
+
+
+def mlp_dropout_mask(seed, step, layer, rows, width, dropout=0.3):
+    """dsp_mlp_dropout_mask: the trainer's keep mask uint8 [rows, width] (1 = kept)."""
+    import torch
+    d = _hip.require_device()
+    mask = torch.empty((rows, width), dtype=torch.uint8, device=d)
+    thr, _ = mlp_drop_threshold(dropout)
+    rc = _hip.lib().dsp_mlp_dropout_mask(int(seed) & 0xFFFFFFFF, int(step), int(layer), int(rows), int(width), thr,
+                                         _hip.ptr(mask), _hip.stream_handle(d))
+    _hip.check(rc, "dsp_mlp_dropout_mask")
+    return mask

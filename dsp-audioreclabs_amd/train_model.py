@@ -5,7 +5,8 @@ a frame length / shift in milliseconds and a window, but through the fused kerne
 directory are decoded once per process (src/dataset.PCMDataset, kept in HBM) and every call is
 one launch over all clips -- the ablation sweeps (ablation_study.py) call it once per setting.
 ``train_and_evaluate`` (:113-...) splits, z-scores and trains as the reference does; the KNN runs
-on the device, the MLP of the reference is outside the accelerated path (src/models.py).
+on the device, and 'mlp' (config.MLP_* unless given, :155-173) with the fused on-device trainer
+(src/models.MLPTrainer).  The default classifier stays 'knn' (the reference's is 'mlp').
 """
 import os
 import sys
@@ -61,8 +62,16 @@ def train_and_evaluate(X, y, classifier_type='knn', test_size=0.2, random_seed=4
     X_test_norm, _, _ = normalize_features(X_test, mean, std)
     if classifier_type == 'knn' and 'n_neighbors' not in classifier_params:
         classifier_params['n_neighbors'] = config.KNN_N_NEIGHBORS
-    clf = create_classifier(classifier_type, **classifier_params)
-    clf.fit(X_train_norm, y_train)
+    if classifier_type == 'mlp':  # :155-173
+        for key, default in (('learning_rate', config.MLP_LEARNING_RATE), ('hidden_layers', config.MLP_HIDDEN_LAYERS),
+                             ('epochs', config.MLP_EPOCHS), ('batch_size', config.MLP_BATCH_SIZE)):
+            classifier_params.setdefault(key, default)
+        clf = create_classifier('mlp', input_size=X_train.shape[1], num_classes=len(np.unique(y)),
+                                **classifier_params)
+        clf.fit(X_train_norm, y_train, verbose=verbose)
+    else:
+        clf = create_classifier(classifier_type, **classifier_params)
+        clf.fit(X_train_norm, y_train)
     res = clf.evaluate(X_test_norm, y_test)
     res['train_accuracy'] = float(np.mean(clf.predict(X_train_norm) == y_train))
     res['classifier'] = clf

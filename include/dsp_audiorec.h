@@ -35,7 +35,10 @@ extern "C" {
                               4: the batch WAV reader (dsp_wav_scan / dsp_wav_read);
                               5: queue_ws is 4 KiB (each counter on its own 256-B line);
                               6: the extraction entry points take out_stride (packed result rows);
-                                 dsp_knn_classify takes flags (DSP_KNN_REF_READY) */
+                                 dsp_knn_classify takes flags (DSP_KNN_REF_READY).
+                              Still 6 with the dsp_mlp_* entry points: they are new symbols only, no
+                              existing signature or meaning changed, so callers built against 6 keep
+                              working (a binding that needs them checks for the symbols) */
 
 /* return codes */
 #define DSP_OK 0
@@ -202,6 +205,74 @@ int dsp_knn_classify(const double *ref, const int32_t *ref_labels, int64_t Nr, c
 int dsp_zscore_fit(const double *X, int64_t N, int D, double *mean, double *std, void *stream);
 int dsp_zscore_apply(const double *X, int64_t N, int D, const double *mean, const double *std,
                      double *out, void *stream);
+
+/*
+ * MLP classifier -- MLPClassifier / MLPTrainer of src/models.py:77-221: Linear -> ReLU -> Dropout per
+ * hidden layer, a last Linear, CrossEntropyLoss (mean over the actual batch), optim.Adam defaults
+ * (betas 0.9 / 0.999, eps 1e-8, bias correction, no weight decay), strictly serial SGD over
+ * shuffled batches.  float32 parameters, activations and accumulation; every sum in a fixed order
+ * (no atomics), so equal inputs give equal bits.
+ *
+ * Packed parameter layout ("params", and the Adam moments m, v): layer after layer, PyTorch's
+ * nn.Linear weight [out, in] row-major, then its bias [out] -- the tensors of the module's
+ * state_dict() in order, flattened.  dsp_mlp_param_count gives the length P.
+ *
+ * Dropout hash (32-bit mixer "lowbias32", all arithmetic mod 2^32):
+ *   mix(x):  x ^= x >> 16;  x *= 0x7feb352d;  x ^= x >> 15;  x *= 0x846ca68b;  x ^= x >> 16
+ *   key  = mix(mix(mix(mix(seed + 0x9e3779b9) ^ low32(step)) ^ high32(step)) ^ layer)
+ *   hash = mix(mix(key ^ row) ^ unit)
+ * seed: the model's seed; step: optimizer steps the model has completed before this one (the
+ * int64 step count, so it runs on across launches); layer: hidden layer index from 0; row: row
+ * within the batch; unit: index within the layer.  A unit is dropped iff hash < drop_threshold
+ * (drop_threshold = floor(p * 2^32); 0 = no dropout); kept units are multiplied by keep_scale,
+ * the float32 value of 1 / (1 - p).  The hash depends on nothing else: not on launch boundaries,
+ * not on n_models, not on the block a model runs in.
+ */
+#define DSP_MLP_MAX_HIDDEN 4
+/* Host helpers.  dsp_mlp_lds_bytes: bytes of LDS dsp_mlp_train needs for batches of up to
+ * batch_size rows, or 0 when the configuration is outside the fused plan (D, every hidden width and
+ * C in 1..64, at most DSP_MLP_MAX_HIDDEN hidden layers, parameters + one batch of activations
+ * within the 160 KiB of one CU).  dsp_mlp_param_count: P (0 for bad sizes). */
+size_t dsp_mlp_lds_bytes(int D, int n_hidden, const int *hidden, int C, int batch_size);
+int64_t dsp_mlp_param_count(int D, int n_hidden, const int *hidden, int C);
+/*
+ * dsp_mlp_train -- MLPTrainer.fit's loop (src/models.py:146-194) for n_models independent models,
+ * one persistent workgroup each, n_epochs epochs in one launch with no host round trip (the
+ * reference syncs once per step, loss.item() :181).
+ *
+ * X          float32 [N, D] (FloatTensor(X_train) :156), y int32 [N] in [0, C) (clamped into it).
+ *            Model k reads X + k * x_stride and y + k * y_stride (in elements): 0 = all models share
+ *            the set (a learning-rate sweep), else >= N * D / >= N: one set per model, all of N rows
+ *            (the window comparison's three feature sets, run_experiments.py:343-376).
+ * hidden     HOST int [n_hidden].
+ * perm       int32 [n_epochs, N] per model: epoch e visits rows perm[e][0..N) in consecutive batches
+ *            of batch_size, the last one short (DataLoader(shuffle=True), drop_last=False :161);
+ *            values are clamped into [0, N).  Model k reads perm + k * perm_stride (in elements):
+ *            0 = all models share one order, else >= n_epochs * N.
+ * params, m, v  float32 [n_models, P], in/out.  steps int64 [n_models], in/out: optimizer steps done.
+ *            A second launch continues exactly where the first stopped.
+ * lr         float64 [n_models] (device).  seeds uint32 [n_models] (device).
+ * loss_hist, acc_hist  float32 [n_models, n_epochs]: per epoch the mean of the batches' mean losses
+ *            (:181,:187) and correct / total over the train-mode outputs, first-index argmax (:182-188).
+ * Returns DSP_ERR_ARGS outside the fused plan (dsp_mlp_lds_bytes == 0).
+ */
+int dsp_mlp_train(const float *X, const int32_t *y, int64_t N, int64_t x_stride, int64_t y_stride, int D,
+                  int n_hidden, const int *hidden, int C, int n_models, int n_epochs, int batch_size,
+                  const int32_t *perm,
+                  int64_t perm_stride, float *params, float *m, float *v, int64_t *steps,
+                  const double *lr, const uint32_t *seeds, uint32_t drop_threshold, float keep_scale,
+                  float *loss_hist, float *acc_hist, void *stream);
+/*
+ * dsp_mlp_predict -- MLPTrainer.predict (src/models.py:196-205): the eval-mode forward pass (no
+ * dropout) of one model over X float32 [Nq, D]; pred int32 [Nq] = first-index argmax (torch.max
+ * :203); logits float32 [Nq, C] or NULL.  64 rows per workgroup, the weights staged in LDS.
+ */
+int dsp_mlp_predict(const float *params, const float *X, int64_t Nq, int D, int n_hidden,
+                    const int *hidden, int C, int32_t *pred, float *logits, void *stream);
+/* Diagnostic: mask uint8 [rows, width] = 1 where the unit is kept, by the trainer's own device
+ * function (nn.Dropout's mask, src/models.py:97). */
+int dsp_mlp_dropout_mask(uint32_t seed, int64_t step, int layer, int rows, int width,
+                         uint32_t drop_threshold, uint8_t *mask, void *stream);
 
 /*
  * Batch WAV reader -- host only (no GPU, no stream): the file side of load_wav
