@@ -1,6 +1,8 @@
-// dsp_device.h -- device helpers shared by the extraction kernels (csrc/extract.hip,
-// csrc/stream.hip): wave reductions on DPP, numpy-order float64 summation (the exact endpoint
-// path), positive-bit / sign-change arithmetic, bit sets of ballots and in-wave bitonic sorts.
+// dsp_device.h -- device helpers shared by the extraction kernels (csrc/extract.hip with
+// extract_generic.h, csrc/general.hip): wave reductions on DPP, numpy-order float64 summation (the
+// exact endpoint path), the p90 ranks, thresholds and near-tie margin of the endpoint scan,
+// positive-bit / sign-change arithmetic, bit sets of ballots, in-wave bitonic sorts and the
+// output-row accessors.
 #ifndef DSP_DEVICE_H
 #define DSP_DEVICE_H
 #include <hip/hip_runtime.h>
@@ -233,7 +235,55 @@ __device__ __forceinline__ double np_lerp(double a, double b, double g)
     const double d = b - a;
     return (g >= 0.5) ? b - d * (1.0 - g) : a + d * g;
 }
+// the three thresholds of the double-threshold scan (:202, :217, :247), each product and sum rounded
+// as numpy rounds it
+struct VadThresholds {
+    double t1, t2, tz;
+};
+template <typename P>  // a kernel's parameter block: the factors p.hi, p.lo, p.zr
+__device__ __forceinline__ VadThresholds vad_thresholds(double p90, double noise_e, double noise_z, const P &p)
+{
+    VadThresholds t;
+    t.t1 = p90 * p.hi;                        // :202
+    t.t2 = noise_e + (p90 - noise_e) * p.lo;  // :217
+    t.tz = noise_z * p.zr;                    // :247
+    return t;
+}
 #pragma clang fp contract(on)
+
+// np.percentile(E, 90) of nv values (:198) = np_lerp(E_(r0), E_(r1), g): the ranks r0 <= r1 of the
+// two order statistics (p90_rank) and the lerp weight g (p90_weight).  Two functions: the wave that
+// selects the order statistics needs no weight, and with both in one the FAST kernel's selection
+// compiled to other instructions.
+template <typename I> struct P90Rank {
+    I r0, r1;
+};
+template <typename I>
+__device__ __forceinline__ P90Rank<I> p90_rank(I nv)
+{
+    const double vi = (double)(nv - 1) * 0.9;
+    P90Rank<I> r;
+    if (vi >= (double)(nv - 1)) {
+        r.r0 = r.r1 = nv - 1;
+    } else {
+        r.r0 = (I)floor(vi);
+        r.r1 = r.r0 + 1;
+    }
+    return r;
+}
+template <typename I>
+__device__ __forceinline__ double p90_weight(I nv)
+{
+    const double vi = (double)(nv - 1) * 0.9;
+    return (vi >= (double)(nv - 1)) ? vi + 1.0 : vi - floor(vi);
+}
+// an energy within the certification margin of a threshold: the decision e > t / e <= t is then
+// redone on the energies in numpy's exact order
+__device__ __forceinline__ bool near_tie(double e, double t)
+{
+    const double d = fabs(e - t);
+    return d <= 1e-11 * fmax(fabs(e), fabs(t)) && !(e == 0.0 && t == 0.0);
+}
 
 // ---- canonical windowed frame sums (both extraction kernels, so that a clip's features do not
 // depend on where it sits in the packed buffer nor on which kernel ran it) ------------------------
@@ -558,6 +608,14 @@ __device__ __forceinline__ K sorted_at(const K (&a)[NH], int r)  // wave-uniform
 {
     return lane_read((NH == 2 && r >= 64) ? a[NH - 1] : a[0], r & 63);
 }
+
+// ---- a clip's output rows, for either kernel's parameter block P ---------------------------------
+// per-array [B,15] / [B,2] / [B] / [B], or rows of p.ostride 4-byte words (ABI 6: one packed
+// [B, DSP_OUT_ROW_WORDS] buffer with the four arrays as column ranges)
+template <typename P> __device__ __forceinline__ float *out_feat(const P &p, int i) { return p.feat + (size_t)i * (p.ostride ? p.ostride : 15); }
+template <typename P> __device__ __forceinline__ int32_t *out_se(const P &p, int i) { return p.start_end + (size_t)i * (p.ostride ? p.ostride : 2); }
+template <typename P> __device__ __forceinline__ int32_t *out_nf(const P &p, int i) { return p.n_frames + (size_t)i * (p.ostride ? p.ostride : 1); }
+template <typename P> __device__ __forceinline__ int32_t *out_st(const P &p, int i) { return p.status + (size_t)i * (p.ostride ? p.ostride : 1); }
 
 }  // namespace dsp
 #endif

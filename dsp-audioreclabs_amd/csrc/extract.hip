@@ -14,6 +14,13 @@
 // compile-time layout), so the other workgroups on the same CU compute while one waits for HBM.
 // Algorithmic traffic: 2 B/sample in + 76 B/clip out.
 //
+// Three kernels.  extract_kernel<true> (clip_fast, this file) serves every launch whose clips fit
+// the compile-time LDS layout; extract_kernel<false> the others, in the layout the host computes
+// (clip_body<false>, extract_generic.h).  extract_exact_kernel follows either on the stream and
+// redoes the rare near ties, always in the runtime layout (clip_body<true>).  This file reads top
+// to bottom: types, the phase helpers of the FAST path (those clip_body shares among them), the
+// clip queue, the steps both clip bodies share, clip_fast, the kernels, the host entry points.
+//
 // Reference functions restated (Hypersonic-cpu/DSP-AudioRecLabs):
 //   preprocess              src/audio_processing.py:78-90
 //   endpoint_detection      src/audio_processing.py:135-275
@@ -118,13 +125,6 @@ struct ExtractParams {
     ExtractCarve cv;             // LDS layout, computed on the host
 };
 
-// the clip's output rows: per-array [B,15] / [B,2] / [B] / [B], or rows of p.ostride 4-byte words
-// (ABI 6: one packed [B, DSP_OUT_ROW_WORDS] buffer with the four arrays as column ranges)
-__device__ __forceinline__ float *out_feat(const ExtractParams &p, int i) { return p.feat + (size_t)i * (p.ostride ? p.ostride : 15); }
-__device__ __forceinline__ int32_t *out_se(const ExtractParams &p, int i) { return p.start_end + (size_t)i * (p.ostride ? p.ostride : 2); }
-__device__ __forceinline__ int32_t *out_nf(const ExtractParams &p, int i) { return p.n_frames + (size_t)i * (p.ostride ? p.ostride : 1); }
-__device__ __forceinline__ int32_t *out_st(const ExtractParams &p, int i) { return p.status + (size_t)i * (p.ostride ? p.ostride : 1); }
-
 static_assert(__is_standard_layout(ExtractParams) && __is_trivially_copyable(ExtractParams),
               "ExtractParams is a plain kernel argument block");
 static_assert(sizeof(ExtractParams) <= 1024, "kernel argument block");
@@ -227,14 +227,6 @@ __device__ __forceinline__ short8 load_cvec(const ExtractParams &p, const ClipRe
 {
     return __builtin_bit_cast(short8, __builtin_amdgcn_raw_buffer_load_b128(clip_rsrc(p, c), 2 * c.lead + 16 * v, 0, 0));
 }
-__device__ __forceinline__ void issue_word(short8 *q, const ExtractParams &p, const ClipRef &c, int w)
-{
-    const __amdgpu_buffer_rsrc_t rs = clip_rsrc(p, c);
-#pragma unroll
-    for (int k = 0; k < 4; k++)
-        q[k] = __builtin_bit_cast(short8, __builtin_amdgcn_raw_buffer_load_b128(rs, 64 * w + 16 * k, 0, 0));
-}
-
 // the clip's first RREG words into registers (word r * NT + tid -> regs[4r .. 4r+3]): one VGPR
 // offset (the thread's word) for all of them, the row in the scalar offset and the vector in the
 // immediate, so no vector instruction runs between the loads (a VGPR rewritten between them made
@@ -305,22 +297,12 @@ __device__ __forceinline__ int vad_scan(const ExtractParams &p, const Ctx &c, in
     Shared *sh = c.sh;
     const double noise_e = sh->noise_e, noise_z = sh->noise_z;  // vad_noise, another wave
     // np.percentile(E, 90) (:198): lerp of the two order statistics found by the workgroup
-    const double vi = (double)(nv - 1) * 0.9;
-    const double g = (vi >= (double)(nv - 1)) ? vi + 1.0 : vi - floor(vi);
+    const double g = p90_weight(nv);
     const double p90 = np_lerp(sh->pa, sh->pb, g);
-    double t1, t2, tz;
     const ExtractParams &q = p;
-    {
-#pragma clang fp contract(off)
-        t1 = p90 * q.hi;                        // :202
-        t2 = noise_e + (p90 - noise_e) * q.lo;  // :217
-        tz = noise_z * q.zr;                    // :247
-    }
+    const VadThresholds th = vad_thresholds(p90, noise_e, noise_z, q);
+    const double t1 = th.t1, t2 = th.t2, tz = th.tz;
     STAMP(c.stamp_clip, 10);
-    auto near = [&](double e, double t) {
-        const double d = fabs(e - t);
-        return d <= 1e-11 * fmax(fabs(e), fabs(t)) && !(e == 0.0 && t == 0.0);
-    };
     int flag = 0, n3 = -1, n1 = 0, n6 = nv - 1;
     auto short_scan = [&](auto kc_t) {
         constexpr int KC = decltype(kc_t)::value;
@@ -334,8 +316,8 @@ __device__ __forceinline__ int vad_scan(const ExtractParams &p, const Ctx &c, in
             hiE.w[k] = __ballot(in && e > t1);
             loE.w[k] = __ballot(in && e <= t2);
             loZ.w[k] = __ballot(in && (double)z <= tz);
-            nr1.w[k] = CERTIFY ? __ballot(in && near(e, t1)) : 0ull;
-            nr2.w[k] = CERTIFY ? __ballot(in && near(e, t2)) : 0ull;
+            nr1.w[k] = CERTIFY ? __ballot(in && near_tie(e, t1)) : 0ull;
+            nr2.w[k] = CERTIFY ? __ballot(in && near_tie(e, t2)) : 0ull;
         }
         n3 = bits_first_ge(hiE, 0);  // :205-213
         const int n4 = bits_last_lt(hiE, nv);
@@ -374,7 +356,7 @@ __device__ __forceinline__ int vad_scan(const ExtractParams &p, const Ctx &c, in
             for (int q0 = 0; q0 < nv; q0 += 64) {
                 const int f = q0 + lane;
                 const bool chk = f < nv && (n3 < 0 || f <= n3 || f >= n4);
-                if (__ballot(chk && near(vE[f], t1))) flag = 1;
+                if (__ballot(chk && near_tie(vE[f], t1))) flag = 1;
             }
         if (n3 >= 0) {
             int n2 = 0, n5 = nv - 1;
@@ -398,7 +380,7 @@ __device__ __forceinline__ int vad_scan(const ExtractParams &p, const Ctx &c, in
                 for (int q0 = 0; q0 < nv; q0 += 64) {
                     const int q = q0 + lane;
                     const bool chk = q < nv && ((q >= n2 - 1 && q < n3) || (q > n4 && q <= n5 + 1));
-                    if (__ballot(chk && near(vE[q], t2))) flag = 1;
+                    if (__ballot(chk && near_tie(vE[q], t2))) flag = 1;
                 }
             for (int q0 = ((n2 - 1) >> 6) << 6; q0 >= 0 && n2 > 0; q0 -= 64) {
                 const int q = q0 + lane;
@@ -427,63 +409,6 @@ __device__ __forceinline__ int vad_scan(const ExtractParams &p, const Ctx &c, in
     return flag;
 }
 
-// Ranks (ties broken by index) of nseq sequences of n elements, element (q, i) = get(q, i).  Wave w
-// compares every element with its chunk of the other elements; the partial counts are combined
-// with integer LDS atomics (exact, order-free).  rk[nseq * n] must be zeroed before the barrier
-// that precedes this call; the ranks are complete after the next barrier.
-template <typename Get>
-__device__ __forceinline__ void rank_partial(Get get, int nseq, int n, int *rk, int wid, int lane)
-{
-    const int per = (n + NWAVE - 1) / NWAVE;
-    const int jlo = wid * per, jhi = min(n, jlo + per);
-    if (jlo >= jhi) return;
-    for (int q = 0; q < nseq; q++)
-        for (int i0 = 0; i0 < n; i0 += 64) {
-            const int i = i0 + lane;
-            const auto e = get(q, i < n ? i : 0);
-            int r = 0;
-#pragma unroll 4
-            for (int j = jlo; j < jhi; j++) {
-                const auto o = get(q, j);
-                r += (o < e) || (o == e && j < i);
-            }
-            if (i < n && r) atomicAdd(&rk[q * n + i], r);
-        }
-}
-
-
-// Order statistics r0 / r1 (ranks with ties broken by index) of v[0..n), n <= 256: every wave
-// holds the whole sequence in registers (lane + 64k), wave w ranks elements w, w + NWAVE, ...
-// with one ballot per chunk.  Lane 0 of the wave that finds them stores them.
-template <typename T, typename Get>
-__device__ __forceinline__ void ballot_select(Get get, int n, int r0, int r1, double *o0, double *o1,
-                                              int wid, int lane)
-{
-    T x[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int j = lane + 64 * k;
-        x[k] = j < n ? get(j) : (T)0;
-    }
-    const int kc = (n + 63) >> 6;
-    for (int i = wid; i < n; i += NWAVE) {
-        const int ki = i >> 6;
-        const T e = lane_read(ki == 0 ? x[0] : ki == 1 ? x[1] : ki == 2 ? x[2] : x[3], i & 63);
-        int r = 0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            if (k < kc) {
-                const int j = lane + 64 * k;
-                r += __popcll(__ballot(j < n && (x[k] < e || (x[k] == e && j < i))));
-            }
-        }
-        if (lane == 0) {
-            if (r == r0) *o0 = (double)e;
-            if (r == r1) *o1 = (double)e;
-        }
-    }
-}
-
 // Endpoint frame ends (pass A): boundary t = 2f (start) / 2f + 1 (end) of VAD frame f lies inside
 // a buffer word that the frame only partly covers; returns that word (or -1: the boundary is
 // word aligned, or t >= 2 nv) and the covered element range [e0, e1) of it.
@@ -507,36 +432,6 @@ __device__ __forceinline__ int vad_partial_word(const ClipRef &cur, int L, int S
     }
     return -1;
 }
-// exact moments (sum k, sum k^2) of elements [e0, e1) of one 32-sample word, branch-free: the
-// range as a bit mask M; pair p's two bits become a 16-bit-lane mask (v_bfe_i32 of each bit,
-// merged by v_bfi), and the pair's masked samples go through one v_dot2 each for sum k and sum k^2
-// (a rolled loop with a branch per element cost ~1.9k instructions per clip, a third of them scalar)
-__device__ __forceinline__ void partial_moments(const short8 (&q)[4], int e0, int e1, int &t1, unsigned long long &t2)
-{
-    const uint32_t hi = e1 >= 32 ? ~0u : (1u << e1) - 1u;
-    const uint32_t M = hi & ~((1u << e0) - 1u);  // e0 < 32
-    const short2v ones = {1, 1};
-    int s1 = 0;
-    unsigned long long s2 = 0;
-    const short8 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];  // value selects (see r1_word)
-#pragma unroll 1
-    for (int k = 0; k < 4; k++) {
-        const short8 v = k == 0 ? q0 : k == 1 ? q1 : k == 2 ? q2 : q3;
-        const uint32_t Mk = M >> (8 * k);
-#pragma unroll
-        for (int h = 0; h < 4; h++) {  // pair 4k + h: elements 8k + 2h, 8k + 2h + 1
-            const uint32_t b0 = (uint32_t)__builtin_amdgcn_sbfe((int)Mk, 2 * h, 1);
-            const uint32_t b1 = (uint32_t)__builtin_amdgcn_sbfe((int)Mk, 2 * h + 1, 1);
-            const uint32_t m = (b0 & 0x0000FFFFu) | (b1 & 0xFFFF0000u);
-            const short2v dm = __builtin_bit_cast(short2v, __builtin_bit_cast(uint32_t, half_pair(v, h)) & m);
-            s1 = __builtin_amdgcn_sdot2(dm, ones, s1, false);
-            s2 += (unsigned)sq2(dm);
-        }
-    }
-    t1 += s1;
-    t2 += s2;
-}
-
 // FAST pass A: partial_moments unrolled over the word's four vectors (no value selects) and with the
 // squares of two pairs chained in one 32-bit v_dot2 (as R1's interior words: 4 x 32768^2 = 2^32
 // wraps only when all four samples are -32768, so a clip holding a -32768 sample (kneg, clip-
@@ -592,9 +487,8 @@ __device__ __forceinline__ uint64_t uni_u64(uint64_t v)
     return ((uint64_t)hi << 32) | lo;
 }
 
-// R1 of one 32-sample buffer word w of a clip (lead, n, nword): exact moments (sum k, sum k^2) to
-// wS1[w] / wS2[w]; the thread's running sum K, min and max (packed int16 min / max for the
-// interior words, whose 32 samples are all the clip's)
+// R1: a thread's running sum K, min and max over its words (packed int16 min / max for the interior
+// words, whose 32 samples are all the clip's)
 struct R1Acc {
     int K, kmin, kmax;
     short2v pmin, pmax;
@@ -608,47 +502,6 @@ __device__ __forceinline__ R1Acc r1_acc_init()
     a.pmin = (short2v){32767, 32767};
     a.pmax = (short2v){-32768, -32768};
     return a;
-}
-__device__ __forceinline__ void r1_word(const short8 *q, int w, int nword, int lead, int n, R1Acc &a, int *wS1,
-                                        unsigned long long *wS2)
-{
-    int s1 = 0;
-    unsigned long long s2 = 0;
-    if (w > 0 && w < nword - 1) {  // all 32 samples are the clip's
-        const short2v ones = {1, 1};
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-#pragma unroll
-            for (int h = 0; h < 4; h++) {
-                const short2v d = half_pair(q[k], h);
-                a.pmin = __builtin_elementwise_min(a.pmin, d);
-                a.pmax = __builtin_elementwise_max(a.pmax, d);
-                s1 = __builtin_amdgcn_sdot2(d, ones, s1, false);
-                s2 += (unsigned)sq2(d);  // <= 2^31: unsigned
-            }
-    } else {  // first / last word of the clip: real samples only
-        // select among values (v_cndmask), never among pointers into the caller's register array:
-        // a pointer select in a rolled loop moves the whole array to scratch
-        const short8 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
-#pragma unroll 1
-        for (int k = 0; k < 4; k++) {
-            const short8 v = k == 0 ? q0 : k == 1 ? q1 : k == 2 ? q2 : q3;
-#pragma unroll
-            for (int e = 0; e < 8; e++) {
-                const int u = 32 * w + 8 * k + e;
-                const int x = v[e];
-                if (u >= lead && u < lead + n) {
-                    s1 += x;
-                    s2 += (unsigned)(x * x);
-                    a.kmin = min(a.kmin, x);
-                    a.kmax = max(a.kmax, x);
-                }
-            }
-        }
-    }
-    wS1[w] = s1;
-    wS2[w] = s2;
-    a.K += s1;
 }
 // R1 of the FAST layout: the interior words from the registers, every lane alike (r1_interior),
 // and the clip's two edge words -- whose samples outside the clip must not count -- by one wave,
@@ -723,19 +576,6 @@ __device__ __forceinline__ void r1_edges(int xv, int nword, int lane, R1Acc &a, 
         __hip_atomic_fetch_add(wS1 + w, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         __hip_atomic_fetch_add(wS2 + w, (unsigned long long)(unsigned)(x * x), __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_WORKGROUP);
-    }
-}
-// the wave's R1 partials -> sh->red_*[wid] (every lane of the wave active)
-__device__ __forceinline__ void r1_reduce(const R1Acc &a, Shared *sh, int wid, int lane)
-{
-    const int kmn = min(a.kmin, min((int)a.pmin.x, (int)a.pmin.y));
-    const int kmx = max(a.kmax, max((int)a.pmax.x, (int)a.pmax.y));
-    const long long ks = (long long)wave_sum(a.K);  // <= 64 threads' sums < 2^31
-    const int wmn = wave_min(kmn), wmx = wave_max(kmx);
-    if (lane == 0) {
-        sh->red_k[wid] = ks;
-        sh->red_a[wid] = wmn;
-        sh->red_b[wid] = wmx;
     }
 }
 // FAST: the R1 partials of each 16-lane row (DPP within the row only) -> 32 slots of LDS per
@@ -829,37 +669,15 @@ __device__ __forceinline__ int zseg_count(const uint32_t *posw, const uint16_t *
     return cnt;
 }
 
-// remove_dc / normalize_audio (:49-75) in sample units, computed redundantly by every thread from
-// the per-wave partial sums in sh->red_*: the reference's float64 mean of k/32768 is exact, so
-// m = fl(K/n) and the peak is max(fl(kmax - m), fl(m - kmin)); a sample is positive after
-// preprocess <=> k >= tpos.
+// remove_dc / normalize_audio (:49-75) in sample units, from the R1 partials: the reference's
+// float64 mean of k/32768 is exact, so m = fl(K/n) and the peak is max(fl(kmax - m), fl(m - kmin));
+// a sample is positive after preprocess <=> k >= tpos.
 struct ClipStats {
     double mq, Mp, invM2;
     float invMf;
     int tpos, t0, nv;
     int kneg;  // the clip holds a -32768 sample (r1_interior's paired squares may have wrapped)
 };
-__device__ __forceinline__ ClipStats clip_stats(const Shared *sh, int n, int L, int S, int do_vad)
-{
-    long long Kt = 0;
-    int kmin = 0x7fffffff, kmax = -0x7fffffff - 1;
-#pragma unroll
-    for (int w = 0; w < NWAVE; w++) {
-        Kt += sh->red_k[w];
-        kmin = min(kmin, sh->red_a[w]);
-        kmax = max(kmax, sh->red_b[w]);
-    }
-    ClipStats s;
-    s.mq = uni((double)Kt / (double)n);
-    s.Mp = uni(fmax((double)kmax - s.mq, s.mq - (double)kmin));
-    s.tpos = uni((int)floor(s.mq) + 1);
-    s.t0 = uni((int)floor(s.mq + 0.5));
-    s.invMf = uni(s.Mp > 0.0 ? (float)(1.0 / s.Mp) : 0.0f);  // as dsp_extract_general (same bits)
-    s.invM2 = uni(s.Mp > 0.0 ? 1.0 / (s.Mp * s.Mp) : 0.0);   // endpoint energies (one rounding)
-    s.nv = (do_vad && n >= L) ? (n - L) / S + 1 : 0;
-    s.kneg = kmin == -32768;
-    return s;
-}
 // clip_stats of the FAST layout, by wave 0 from r1_reduce_rows's 32 row partials (one per lane)
 __device__ __forceinline__ ClipStats clip_stats_rows(const Ctx &c, int lane, int n, int L, int S, int do_vad)
 {
@@ -888,14 +706,8 @@ __device__ __forceinline__ ClipStats clip_stats_rows(const Ctx &c, int lane, int
 // ms, profiles/r05rs_ab_select.txt; removed)
 __device__ __forceinline__ void p90_select_wave(const Ctx &c, int nv, int lane)
 {
-    const double vi = (double)(nv - 1) * 0.9;
-    int r0, r1;
-    if (vi >= (double)(nv - 1)) {
-        r0 = r1 = nv - 1;
-    } else {
-        r0 = (int)floor(vi);
-        r1 = r0 + 1;
-    }
+    const P90Rank<int> pr = p90_rank(nv);
+    const int r0 = pr.r0, r1 = pr.r1;
     const bool in0 = lane < nv, in1 = lane + 64 < nv;
     const unsigned long long f0 = in0 ? dkey(c.vE[lane]) : 0ull;  // pads: below every real key
     const unsigned long long f1 = in1 ? dkey(c.vE[lane + 64]) : 0ull;
@@ -1225,7 +1037,6 @@ __device__ __forceinline__ void r5_fast(const Ctx &c, int F, float *featb, int w
         }
     }
 }
-
 // Clip queue (ABI 5).  p.queue: the caller's zeroed 4 KiB scratch, words 0-7 the claim counters
 // of eight ranges of clip chunks (p.qchunk consecutive clips each), word 8 the count of workgroups
 // done.  Workgroup b's first chunk is chunk b, taken without a claim; the chunks after the first G
@@ -1343,76 +1154,35 @@ __device__ __forceinline__ void queue_done(const ExtractParams &p)
     }
 }
 
-// One clip, start to finish; its first RREG words are already in flight into regs (word
-// r * NT + tid in regs[4r .. 4r+3]).  EXACT = false: endpoint energies from exact moments,
-// decisions certified; returns false on a near tie (the clip is then redone with EXACT = true
-// after the persistent loop).
-// FAST: the compile-time LDS layout (extract_carve_fast); the clip is in registers and there are
-// at most 128 VAD and feature frames, so the long-clip paths drop out
-struct NoClaim {
-    __device__ int operator()() const { return -1; }
-};
-template <bool EXACT, bool FAST, typename Resolve = NoClaim>
-__device__ __forceinline__ bool clip_body(const ExtractParams &p, const Ctx &c, int i, const ClipRef &cur,
-                                          short8 (&regs)[NRV], Resolve resolve = NoClaim())
+// ---- steps that clip_fast and clip_body share ----------------------------------------------------
+// diagnostic build: the clip's loads landed (stamp 13; per wave: 24 + wave)
+__device__ __forceinline__ void stamp_loads_landed(const ExtractParams &p, int i, int wid, int lane)
 {
-    Shared *sh = c.sh;
-    // (the generic layout's and the exact redo's index arithmetic spills when hoisted: opaque
-    // thread index there)
-    const int tid = (FAST && !EXACT) ? (int)threadIdx.x : opaque_tid(), lane = tid & 63,
-              wid = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform: scalar branches
-    // frame sizes opaque per clip as well: constants derived from them ((double)L, ...) are
-    // recomputed in the clip instead of being kept live across the loop
-    int L = p.L, S = p.S;
-    asm volatile("" : "+s"(L), "+s"(S));
-    const int n = cur.n, lead = cur.lead, nword = cur.nword;
-    // outputs: the main kernel stages them in LDS (slot i mod EXTRACT_OSTAGE) and the workgroup
-    // writes a chunk's clips together (flush_outputs); the exact redo writes them directly
-    const int oslot = i & (EXTRACT_OSTAGE - 1);
-    float *featb = EXACT ? out_feat(p, i) : reinterpret_cast<float *>(c.orow + DSP_OUT_ROW_WORDS * oslot);
-    const int16_t *clip_g = p.pcm + cur.base + lead;  // the clip in global memory, sample coords
-    STAMP(i, 0);
 #ifdef DSP_STAMPS
-    if (p.stamps) {  // diagnostic build: the clip's loads landed (stamp 13; per wave: 24 + wave)
+    if (p.stamps) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         STAMP(i, 13);
         if (lane == 0) p.stamps[(size_t)i * 32 + 24 + wid] = __builtin_amdgcn_s_memtime();
     }
 #endif
-
-    // ---- R1: integer sum / min / max; exact moments per 32-sample word -----------------------
-    R1Acc acc = r1_acc_init();  // K <= RREG * 32 * 32768 per thread (longer clips: one word per trip)
-    // clips of up to RREG * NT words stream from the registers loaded before this call; longer
-    // ones are read word by word here and again in R2 (the second read hits L2)
-    const bool inreg = FAST || nword <= RREG * NT;
-    if (inreg) {
-#pragma unroll
-        for (int r = 0; r < RREG; r++) {
-            const int w = r * NT + tid;
-            if (w < nword) r1_word(&regs[4 * r], w, nword, lead, n, acc, c.wS1, c.wS2);
-        }
-    } else {
-#pragma unroll 1
-        for (int w = tid; w < nword; w += NT) {
-            short8 q[4];
-            issue_word(q, p, cur, w);
-            r1_word(q, w, nword, lead, n, acc, c.wS1, c.wS2);
-        }
-    }
-    r1_reduce(acc, sh, wid, lane);
-    __syncthreads();
-    if (!EXACT && tid == 0 && sh->sclear) {  // the last flush's slots (every thread has read them)
+}
+// after the R1 barrier: thread 0 forgets the slots of the last flush (every thread has read them)
+__device__ __forceinline__ void reset_staged(Shared *sh, int tid)
+{
+    if (tid == 0 && sh->sclear) {
         sh->smask = 0;
         sh->schunk = -1;
         sh->sclear = 0;
     }
-    // wave 0 computes the clip statistics once and shares them (a second barrier), instead of
-    // every wave repeating the fp64 work (3.415 -> 3.386 ms at 100k clips, round 4)
-    if (wid == 0) {
-        const ClipStats c0 = clip_stats(sh, n, L, S, p.do_vad);
-        if (lane == 0) sh->cs = {c0.mq, c0.Mp, c0.invM2, c0.invMf, c0.tpos, c0.t0, c0.nv, c0.kneg};
-    }
-    __syncthreads();
+}
+// wave 0 computes the clip statistics once and shares them through sh->cs (a second barrier),
+// instead of every wave repeating the fp64 work (3.415 -> 3.386 ms at 100k clips, round 4)
+__device__ __forceinline__ void share_clip_stats(Shared *sh, const ClipStats &c0, int lane)
+{
+    if (lane == 0) sh->cs = {c0.mq, c0.Mp, c0.invM2, c0.invMf, c0.tpos, c0.t0, c0.nv, c0.kneg};
+}
+__device__ __forceinline__ ClipStats shared_clip_stats(const Shared *sh)
+{
     ClipStats cs;
     cs.mq = uni(sh->cs.mq);
     cs.Mp = uni(sh->cs.Mp);
@@ -1421,264 +1191,41 @@ __device__ __forceinline__ bool clip_body(const ExtractParams &p, const Ctx &c, 
     cs.tpos = uni(sh->cs.tpos);
     cs.t0 = uni(sh->cs.t0);
     cs.nv = uni(sh->cs.nv);
-    const double mq = cs.mq, Mp = cs.Mp;
-    const int tpos = cs.tpos, t0 = cs.t0, nv = cs.nv;
-    STAMP(i, 1);
-
-    // ---- R2: positive-sample bits, one 32-bit word per 32 buffer samples ---------------------
-    if (inreg) {
-#pragma unroll
-        for (int r = 0; r < RREG; r++) {
-            const int w = r * NT + tid;
-            if (w < nword) c.posw[w] = (DSP_ABL & 4) ? 0u : pos_word(&regs[4 * r], w, nword, lead, n, tpos);
-        }
-    } else {
-#pragma unroll 1
-        for (int w = tid; w < nword; w += NT) {
-            short8 q[4];
-            issue_word(q, p, cur, w);
-            c.posw[w] = pos_word(q, w, nword, lead, n, tpos);
-        }
+    cs.kneg = uni(sh->cs.kneg);
+    return cs;
+}
+// the crop [st, en) from the scan's decisions (sh->n3 < 0: no high-energy frame, the whole clip)
+__device__ __forceinline__ void crop_from_scan(const Shared *sh, int L, int S, int n, int &st, int &en)
+{
+    if (sh->n3 >= 0) {
+        st = sh->n1 * S;              // :272
+        en = min(sh->n6 * S + L, n);  // :273
     }
-    if (tid < 2) c.posw[nword + tid] = 0;
-    // the partial words that endpoint pass A needs (FAST: one frame end per thread), issued
-    // before the barrier so that they are in flight while the workgroup synchronises
-    short8 qa[4];
-    int pa_w = -1, pa_e0 = 0, pa_e1 = 0;
-    if constexpr (!EXACT) {
-        if constexpr (FAST) pa_w = vad_partial_issue(p, cur, L, S, nv, tid, qa, pa_e0, pa_e1);
-    }
-    __syncthreads();
-    STAMP(i, 2);
-
-    // ---- R3: endpoint detection (:161-273) ------------------------------------------------
-    int st = 0, en = n;
-    if (nv > 0) {
-        // frame f = buffer samples [u0, u0 + L): exact moments from the word sums plus the two
-        // partial words at its ends, sign changes from the bits.
-        // Pass A, one thread per frame end: the partial word's moments (FAST: loaded before the
-        // next clip's prefetch; otherwise re-read from L2 here).
-        if constexpr (FAST && !EXACT) {
-            vad_frames_fast(c, cur, L, S, cs, qa, pa_w, pa_e0, pa_e1, tid);
-            STAMP(i, 7);
-        } else {
-            {
-                if constexpr (!EXACT) {
-                    {  // generic layout: the partial words re-read from L2 here
-                        for (int t = tid; t < 2 * nv; t += NT) {
-                            int e0, e1, t1 = 0;
-                            unsigned long long t2 = 0;
-                            const int pw = vad_partial_word(cur, L, S, nv, t, e0, e1);
-                            if (pw >= 0) {
-                                short8 q[4];
-    #pragma unroll
-                                for (int k = 0; k < 4; k++) q[k] = load_vec(p, cur, 4 * pw + k);
-                                partial_moments(q, e0, e1, t1, t2);
-                            }
-                            c.pS1[t] = t1;
-                            c.pS2[t] = t2;
-                        }
-                    }
-                    __syncthreads();
-                    STAMP(i, 7);
-                }
-                // Pass B, one quad per frame: interior word sums and sign changes, each lane a
-                // contiguous quarter
-                const int q4 = tid >> 2, lq = tid & 3;
-                for (int f0 = 0; f0 < nv; f0 += NT / 4) {
-                    const int f = f0 + q4;
-                    const bool act = f < nv;
-                    int s1 = 0;  // |frame sum| <= L * 32768 < 2^31 for L < 65536
-                    unsigned long long s2 = 0;
-                    int zc = 0;
-                    if (act) {
-                        const int u0 = lead + f * S, u1 = u0 + L;
-                        if (!EXACT) {
-                            const int wa = u0 >> 5, wb = (u1 - 1) >> 5;
-                            const int wi0 = (u0 & 31) ? wa + 1 : wa, wi1 = (u1 & 31) ? wb - 1 : wb;
-                            const int per = (wi1 - wi0 + 4) >> 2;
-                            const int ws = wi0 + lq * per, we = min(ws + per - 1, wi1);
-    #pragma unroll 3
-                            for (int w = ws; w <= we; w++) {
-                                s1 += c.wS1[w];
-                                s2 += c.wS2[w];
-                            }
-                            if (lq == 0) {
-                                s1 += c.pS1[2 * f] + c.pS1[2 * f + 1];
-                                s2 += c.pS2[2 * f] + c.pS2[2 * f + 1];
-                            }
-                        }
-                        const int np_ = L - 1, pq = (np_ + 3) >> 2;  // pairs [u0, u1 - 1) in quarters
-                        const int x0 = u0 + min(lq * pq, np_), x1 = u0 + min((lq + 1) * pq, np_);
-                        zc = chg_run(c.posw, x0, x1);
-                    }
-                    s1 = dpp_quad_reduce(s1, OpAdd());
-                    s2 = dpp_quad_sum64(s2);
-                    zc = dpp_quad_reduce(zc, OpAdd());
-                    if (act && lq == 0) {
-                        if (!FAST) c.rank[f] = 0;
-                        c.vE[f] = EXACT ? np_energy_exact(clip_g, f * S, L, mq, Mp)
-                                        : energy_from_moments(s2, s1, L, t0, mq - (double)t0, cs.invM2);
-                        c.vZ[f] = zc;
-                    }
-                }
-            }
+}
+// the optional dump of the VAD frames' energies and sign changes
+__device__ __forceinline__ void dump_vad(const ExtractParams &p, const Ctx &c, int i, int nv)
+{
+    if (p.vad_energy)
+        for (int f = opaque_tid(); f < nv && f < p.ld_vad; f += NT) {
+            p.vad_energy[(size_t)i * p.ld_vad + f] = c.vE[f];
+            p.vad_zcr[(size_t)i * p.ld_vad + f] = c.vZ[f];
         }
-        __syncthreads();
-        STAMP(i, 8);
-        {
-            // p90 order statistics (:198)
-            {
-                const double vi = (double)(nv - 1) * 0.9;
-                int r0, r1;
-                if (vi >= (double)(nv - 1)) {
-                    r0 = r1 = nv - 1;
-                } else {
-                    r0 = (int)floor(vi);
-                    r1 = r0 + 1;
-                }
-                if (FAST || nv <= 128) {
-                    // wave 0: bitonic sort of the high halves of the order-preserving keys; the rank's
-                    // element is the one holding that high half, or, when several do, the one of the
-                    // right rank among them by the full key
-                    if (wid == 0) {
-                        // the workgroup's critical path (p90, then the scan) runs on this one wave:
-                        // it takes issue priority over the co-resident workgroup's waves until the
-                        // decisions are made (2% at 100k clips)
-                        __builtin_amdgcn_s_setprio(2);
-                        p90_select_wave(c, nv, lane);
-                    }
-                } else if (nv <= 256) {
-                    ballot_select<double>([&](int j) { return c.vE[j]; }, nv, r0, r1, &sh->pa, &sh->pb, wid, lane);
-                } else {  // long clips: partial ranks over all waves
-                    rank_partial([&](int, int j) { return c.vE[j]; }, 1, nv, c.rank, wid, lane);
-                    __syncthreads();
-                    for (int f = tid; f < nv; f += NT) {
-                        const int r = c.rank[f];
-                        if (r == r0) sh->pa = c.vE[f];
-                        if (r == r1) sh->pb = c.vE[f];
-                    }
-                }
-            }
-            if (wid == 1 % NWAVE) vad_noise(c, nv, lane);  // beside wave 0's p90 selection
-            __syncthreads();
-        }
-        STAMP(i, 3);
-        if (wid == 0) {
-            const int flag = vad_scan<!EXACT, FAST>(p, c, nv, lane);
-            if (lane == 0) sh->exact = (!EXACT && Mp > 0.0) ? flag : 0;
-            __builtin_amdgcn_s_setprio(0);
-        }
-        __syncthreads();
-        if (!EXACT && sh->exact) {  // near tie: redo in numpy's exact order after the loop
-            return false;
-        }
-        if (sh->n3 >= 0) {
-            st = sh->n1 * S;              // :272
-            en = min(sh->n6 * S + L, n);  // :273
-        }
-        if (p.vad_energy)
-            for (int f = opaque_tid(); f < nv && f < p.ld_vad; f += NT) {
-                p.vad_energy[(size_t)i * p.ld_vad + f] = c.vE[f];
-                p.vad_zcr[(size_t)i * p.ld_vad + f] = c.vZ[f];
-            }
-    }
-    STAMP(i, 4);
-
-    // ---- R4: windowed frames over the crop [st, en) (r4_frames) --------------------------------
-    const int F = r4_frames<false>(p, c, cur, L, S, st, en, cs, sh->j0, sh->j1, wid, lane);
-    STAMP(i, 12);
-    if (!FAST && F > 128)
-        for (int t = tid; t < 3 * F; t += NT) c.rank[t] = 0;
-    if constexpr (!EXACT)
-        if (tid == 0) sh->next = resolve();  // claimed at the clip's start (-1: none)
-    __syncthreads();
-    if constexpr (!EXACT) {
-        // regs are dead since R2: the next clip's words load while R5 runs (unconditional, a
-        // clip_none() reads zeros, so the compiler's vmcnt bookkeeping stays exact)
-        const int nx = sh->next;
-        issue_clip(regs, p, nx >= 0 ? clip_ref(p, nx) : clip_none(), tid);
-    }
-    STAMP(i, 5);
-
-    // ---- R5: 15-d statistics (compute_statistics x 3, fe.py:46-62) ------------------------
-    // np.median: the middle order statistic (odd F) or the mean of the two middle ones
-    const int r0 = (F - 1) / 2, r1 = F / 2;
-    {
-        if (FAST || F <= 128) {
-            r5_fast(c, F, featb, wid, lane);
-        } else {  // long sequences: partial ranks over all waves, then one wave per sequence
-            rank_partial([&](int q, int j) { return q == 2 ? (float)c.fZ[j] : (q == 0 ? c.fE[j] : c.fM[j]); },
-                         3, F, c.rank, wid, lane);
-            __syncthreads();
-            for (int t = tid; t < 3 * F; t += NT) {
-                const int q = t / F, e = t - q * F;
-                const int r = c.rank[t];
-                const double val = q == 2 ? (double)c.fZ[e] : (double)(q == 0 ? c.fE[e] : c.fM[e]);
-                if (r == r0) sh->oslo[q] = val;
-                if (r == r1) sh->oshi[q] = val;
-            }
-            __syncthreads();
-            if (wid < 3) {
-                double s = 0.0, mx = -INFINITY, mn = INFINITY;
-                for (int q = lane; q < F; q += 64) {
-                    const double x = wid == 0 ? (double)c.fE[q] : wid == 1 ? (double)c.fM[q] : (double)c.fZ[q];
-                    s += x;
-                    mx = fmax(mx, x);
-                    mn = fmin(mn, x);
-                }
-                s = wave_sum(s);
-                mx = wave_maxd(mx);
-                mn = wave_mind(mn);
-                const double mean = s / (double)F;
-                double qq = 0.0;
-                for (int q = lane; q < F; q += 64) {
-                    const double x = wid == 0 ? (double)c.fE[q] : wid == 1 ? (double)c.fM[q] : (double)c.fZ[q];
-                    const double d = x - mean;
-                    qq = fma(d, d, qq);
-                }
-                qq = wave_sum(qq);
-                double med;
-                {
-#pragma clang fp contract(off)
-                    med = (F & 1) ? sh->oshi[wid] : (sh->oslo[wid] + sh->oshi[wid]) / 2.0;
-                }
-                if (lane < 5) {
-                    const double o = lane == 0 ? mean : lane == 1 ? sqrt(qq / (double)F) : lane == 2 ? mx
-                                     : lane == 3 ? mn : med;
-                    featb[5 * wid + lane] = (float)o;
-                }
-            }
-        }
-    }
-    STAMP(i, 9);
-    if (p.seq)
-        for (int g = tid; g < F && g < p.ld_seq; g += NT) {
-            float *o = p.seq + ((size_t)i * p.ld_seq + g) * 3;
-            o[0] = c.fE[g];
-            o[1] = c.fM[g];
-            o[2] = (float)c.fZ[g];
-        }
-    if (tid == 0) {
-        if constexpr (EXACT) {
-            out_se(p, i)[0] = st;
-            out_se(p, i)[1] = en;
-            *out_nf(p, i) = F;
-            *out_st(p, i) = DSP_CLIP_OK | DSP_CLIP_FLAG_VAD_EXACT;
-        } else {
-            int32_t *orow = c.orow + DSP_OUT_ROW_WORDS * oslot;
-            orow[15] = st;
-            orow[16] = en;
-            orow[17] = F;
-            orow[18] = DSP_CLIP_OK;
-            const int ch = i / EXTRACT_OSTAGE;  // the staged slots belong to chunk sh->schunk
-            const unsigned m0 = sh->schunk == ch ? sh->smask : 0u;
-            sh->schunk = ch;
-            sh->smask = m0 | (1u << oslot);
-        }
-    }
-    STAMP(i, 6);
-    return true;
+}
+// thread 0: start / end / frames / status beside the staged features of clip i (slot i mod
+// EXTRACT_OSTAGE of the chunk's rows; flush_outputs writes the slots in sh->smask)
+__device__ __forceinline__ void stage_outputs(const Ctx &c, int i, int st, int en, int F)
+{
+    Shared *sh = c.sh;
+    const int oslot = i & (EXTRACT_OSTAGE - 1);
+    int32_t *orow = c.orow + DSP_OUT_ROW_WORDS * oslot;
+    orow[15] = st;
+    orow[16] = en;
+    orow[17] = F;
+    orow[18] = DSP_CLIP_OK;
+    const int ch = i / EXTRACT_OSTAGE;  // the staged slots belong to chunk sh->schunk
+    const unsigned m0 = sh->schunk == ch ? sh->smask : 0u;
+    sh->schunk = ch;
+    sh->smask = m0 | (1u << oslot);
 }
 
 // ==== FAST launches: clip_fast =================================================================
@@ -1714,13 +1261,7 @@ __device__ __forceinline__ bool clip_fast(const ExtractParams &p, const Ctx &c, 
     const int oslot = i & (EXTRACT_OSTAGE - 1);
     float *featb = reinterpret_cast<float *>(c.orow + DSP_OUT_ROW_WORDS * oslot);
     STAMP(i, 0);
-#ifdef DSP_STAMPS
-    if (p.stamps) {  // diagnostic build: the clip's loads landed (stamp 13; per wave: 24 + wave)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        STAMP(i, 13);
-        if (lane == 0) p.stamps[(size_t)i * 32 + 24 + wid] = __builtin_amdgcn_s_memtime();
-    }
-#endif
+    stamp_loads_landed(p, i, wid, lane);
 
     // ---- R1: integer sum / min / max; exact moments per 32-sample word --------------------------
     MARK(R1);
@@ -1734,26 +1275,11 @@ __device__ __forceinline__ bool clip_fast(const ExtractParams &p, const Ctx &c, 
     MARK(R1red);
     r1_reduce_rows(acc, c, wid, lane);
     __syncthreads();
-    if (tid == 0 && sh->sclear) {  // the last flush's slots (every thread has read them by now)
-        sh->smask = 0;
-        sh->schunk = -1;
-        sh->sclear = 0;
-    }
+    reset_staged(sh, tid);
     MARK(stats);
-    if (wid == 0) {  // the clip statistics once, shared through LDS
-        const ClipStats c0 = clip_stats_rows(c, lane, n, L, S, p.do_vad);
-        if (lane == 0) sh->cs = {c0.mq, c0.Mp, c0.invM2, c0.invMf, c0.tpos, c0.t0, c0.nv, c0.kneg};
-    }
+    if (wid == 0) share_clip_stats(sh, clip_stats_rows(c, lane, n, L, S, p.do_vad), lane);
     __syncthreads();
-    ClipStats cs;
-    cs.mq = uni(sh->cs.mq);
-    cs.Mp = uni(sh->cs.Mp);
-    cs.invM2 = uni(sh->cs.invM2);
-    cs.invMf = uni(sh->cs.invMf);
-    cs.tpos = uni(sh->cs.tpos);
-    cs.t0 = uni(sh->cs.t0);
-    cs.nv = uni(sh->cs.nv);
-    cs.kneg = uni(sh->cs.kneg);
+    const ClipStats cs = shared_clip_stats(sh);
     const int nv = cs.nv;
     STAMP(i, 1);
 
@@ -1834,16 +1360,8 @@ __device__ __forceinline__ bool clip_fast(const ExtractParams &p, const Ctx &c, 
     int st = 0, en = n;
     if (nv > 0) {
         if (sh->exact) return false;  // near tie: redone in numpy's exact order by the exact kernel
-        if (sh->n3 >= 0) {
-            st = sh->n1 * S;              // :272
-            en = min(sh->n6 * S + L, n);  // :273
-        }
-        const ExtractParams &q = p;
-        if (q.vad_energy)
-            for (int f = opaque_tid(); f < nv && f < q.ld_vad; f += NT) {
-                q.vad_energy[(size_t)i * q.ld_vad + f] = c.vE[f];
-                q.vad_zcr[(size_t)i * q.ld_vad + f] = c.vZ[f];
-            }
+        crop_from_scan(sh, L, S, n, st, en);
+        dump_vad(p, c, i, nv);
     }
     STAMP(i, 4);
 
@@ -1867,6 +1385,8 @@ __device__ __forceinline__ bool clip_fast(const ExtractParams &p, const Ctx &c, 
     }
     STAMP(i, 9);
     MARK(tail);
+    // (this loop and its alias stay here: shared with clip_body as a helper, extract_kernel<true>
+    // grew by 141 instructions and one SGPR spill)
     const ExtractParams &qs = p;
     if (qs.seq)
         for (int g = tid; g < F && g < qs.ld_seq; g += NT) {
@@ -1875,17 +1395,7 @@ __device__ __forceinline__ bool clip_fast(const ExtractParams &p, const Ctx &c, 
             o[1] = c.fM[g];
             o[2] = (float)c.fZ[g];
         }
-    if (tid == 0) {
-        int32_t *orow = c.orow + DSP_OUT_ROW_WORDS * oslot;
-        orow[15] = st;
-        orow[16] = en;
-        orow[17] = F;
-        orow[18] = DSP_CLIP_OK;
-        const int ch = i / EXTRACT_OSTAGE;  // the staged slots belong to chunk sh->schunk
-        const unsigned m0 = sh->schunk == ch ? sh->smask : 0u;
-        sh->schunk = ch;
-        sh->smask = m0 | (1u << oslot);
-    }
+    if (tid == 0) stage_outputs(c, i, st, en, F);
     STAMP(i, 6);
     return true;
 }
@@ -2017,6 +1527,13 @@ __device__ __forceinline__ void flush_outputs(const ExtractParams &p, const Ctx 
 // registers: a 512-thread workgroup puts 2 waves on each SIMD, so W workgroups per CU allow
 // 512 / (2 W) VGPRs -- FAST 80 (three per CU), generic 128 (two per CU)
 
+}  // namespace dsp
+
+// the runtime layout's clip body (clip_body) and the helpers only it uses
+#include "extract_generic.h"
+
+namespace dsp {
+
 // ---- one clip at a time per workgroup (both layouts) --------------------------------------------
 // A near tie (an endpoint decision within the certification margin) leaves the clip with status
 // DSP_CLIP_UNCERTIFIED; extract_exact_kernel, launched next on the stream, redoes it.
@@ -2082,7 +1599,7 @@ void extract_kernel(ExtractParams p)
                 // resolves sh->next itself (before the crop), also for a deferred clip
                 done = clip_fast(p, c, i, cur, regs, [&]() { return queue_end(Q, sh, cl); });
             } else {
-                done = clip_body<false, false>(p, c, i, cur, regs, [&]() { return queue_end(Q, sh, cl); });
+                done = clip_body<false>(p, c, i, cur, regs, [&]() { return queue_end(Q, sh, cl); });
                 if (!done && tid == 0) sh->next = queue_end(Q, sh, cl);  // a deferred clip returns before R4
             }
             if (!done && tid == 0) {
@@ -2118,16 +1635,17 @@ void extract_kernel(ExtractParams p)
 // (numpy-order) energy path, and gets its final outputs and DSP_CLIP_FLAG_VAD_EXACT.  With the
 // clip queue, extract_kernel counts its near ties in queue word 9: a launch with none returns at
 // once (one load per workgroup); otherwise the last workgroup out zeroes words 9 and 10 again.
-template <bool FAST>
+// One kernel for both launch kinds: it always works in the runtime layout p.cv, which holds any clip
+// of the launch (a FAST launch's clips take in it the branches the compile-time layout hard-wires).
 __global__ __launch_bounds__(NT) void extract_exact_kernel(ExtractParams p)
 {
     if (p.queue && __hip_atomic_load(qword(p.queue, 9), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) return;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    Ctx c = make_ctx<FAST>(p, lds);
+    Ctx c = make_ctx<false>(p, lds);
     Shared *sh = c.sh;
     const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     // NT ints past the layout (the host launches this kernel with 4 NT more bytes of LDS)
-    int *list = reinterpret_cast<int *>(lds + (FAST ? extract_carve_fast().total : p.cv.total));
+    int *list = reinterpret_cast<int *>(lds + p.cv.total);
     bool built = false;
     // the workgroup's clips blockIdx.x + G (t + NT k), NT statuses read at once, the near ties listed
     for (int64_t b0 = 0; b0 < p.B; b0 += (int64_t)gridDim.x * NT) {
@@ -2148,7 +1666,7 @@ __global__ __launch_bounds__(NT) void extract_exact_kernel(ExtractParams p)
             const ClipRef cr = clip_ref(p, ci);
             short8 regs[NRV];
             issue_clip(regs, p, cr);
-            clip_body<true, FAST>(p, c, ci, cr, regs);
+            clip_body<true>(p, c, ci, cr, regs);
             __syncthreads();
         }
     }
@@ -2219,9 +1737,7 @@ extern "C" int dsp_extract_features(const int16_t *pcm, const int64_t *offsets, 
                                   hipFuncAttributeMaxDynamicSharedMemorySize, EXTRACT_LDS_LIMIT);
         (void)hipFuncSetAttribute((const void *)dsp::extract_kernel<false>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, EXTRACT_LDS_LIMIT);
-        (void)hipFuncSetAttribute((const void *)dsp::extract_exact_kernel<true>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, EXTRACT_LDS_LIMIT);
-        (void)hipFuncSetAttribute((const void *)dsp::extract_exact_kernel<false>,
+        (void)hipFuncSetAttribute((const void *)dsp::extract_exact_kernel,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, EXTRACT_LDS_LIMIT);
     }
     const int num_cus = g_num_cus[dev];
@@ -2271,13 +1787,10 @@ extern "C" int dsp_extract_features(const int16_t *pcm, const int64_t *offsets, 
     // the near-tie redo: one workgroup per CU (near ties are rare; a launch without any returns at
     // once, and dispatching a third of the main grid makes that empty launch shorter)
     const int xgrid = std::min(grid, num_cus);
-    if (fast) {
-        hipLaunchKernelGGL(dsp::extract_kernel<true>, dim3(grid), dim3(dsp::NT), lds_launch, s, p);
-        hipLaunchKernelGGL(dsp::extract_exact_kernel<true>, dim3(xgrid), dim3(dsp::NT), lds_launch + 4 * dsp::NT, s, p);
-    } else {
-        hipLaunchKernelGGL(dsp::extract_kernel<false>, dim3(grid), dim3(dsp::NT), lds_launch, s, p);
-        hipLaunchKernelGGL(dsp::extract_exact_kernel<false>, dim3(xgrid), dim3(dsp::NT), lds_launch + 4 * dsp::NT, s, p);
-    }
+    if (fast) hipLaunchKernelGGL(dsp::extract_kernel<true>, dim3(grid), dim3(dsp::NT), lds_launch, s, p);
+    else hipLaunchKernelGGL(dsp::extract_kernel<false>, dim3(grid), dim3(dsp::NT), lds_launch, s, p);
+    // (the runtime layout on both paths: lds + 4 NT <= EXTRACT_LDS_LIMIT by dsp_extract_lds_bytes)
+    hipLaunchKernelGGL(dsp::extract_exact_kernel, dim3(xgrid), dim3(dsp::NT), lds + 4 * dsp::NT, s, p);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? DSP_OK : DSP_ERR_HIP + (int)e;
 }

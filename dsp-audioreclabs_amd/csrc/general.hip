@@ -52,11 +52,6 @@ struct Params {
     int64_t nvcap, fcap;
 };
 
-__device__ __forceinline__ float *out_feat(const Params &p, int i) { return p.feat + (int64_t)i * (p.ostride ? p.ostride : 15); }
-__device__ __forceinline__ int32_t *out_se(const Params &p, int i) { return p.start_end + (int64_t)i * (p.ostride ? p.ostride : 2); }
-__device__ __forceinline__ int32_t *out_nf(const Params &p, int i) { return p.n_frames + (int64_t)i * (p.ostride ? p.ostride : 1); }
-__device__ __forceinline__ int32_t *out_st(const Params &p, int i) { return p.status + (int64_t)i * (p.ostride ? p.ostride : 1); }
-
 // workspace of one clip: vE f64[nvcap], vZ i32[nvcap], fE f32[fcap], fM f32[fcap], fZ i32[fcap],
 // keys u64[max(nvcap, fcap)]
 struct Ws {
@@ -285,18 +280,10 @@ __device__ __forceinline__ void general_clip(const Params &p, Sh &s, const Ws &w
             // p90 (:198): order statistics of the energies by radix selection
             for (int64_t f = tid; f < nv; f += NT) w.key[f] = dkey(w.vE[f]);
             __syncthreads();
-            const double vi = (double)(nv - 1) * 0.9;
-            int64_t r0, r1;
-            if (vi >= (double)(nv - 1)) {
-                r0 = r1 = nv - 1;
-            } else {
-                r0 = (int64_t)floor(vi);
-                r1 = r0 + 1;
-            }
-            const double pa = dkey_value(radix_select<8>(s, w.key, nv, r0));
-            const double pb = dkey_value(radix_select<8>(s, w.key, nv, r1));
-            const double g = (vi >= (double)(nv - 1)) ? vi + 1.0 : vi - floor(vi);
-            const double p90 = np_lerp(pa, pb, g);
+            const P90Rank<int64_t> pr = p90_rank(nv);
+            const double pa = dkey_value(radix_select<8>(s, w.key, nv, pr.r0));
+            const double pb = dkey_value(radix_select<8>(s, w.key, nv, pr.r1));
+            const double p90 = np_lerp(pa, pb, p90_weight(nv));
             if (tid == 0) {
                 // noise estimates (:188-195, :239-245), numpy order for the small sums
                 const int64_t nfr = min((int64_t)5, nv / 10);
@@ -316,17 +303,8 @@ __device__ __forceinline__ void general_clip(const Params &p, Sh &s, const Ws &w
                     }
                     noise_z = (double)mz;
                 }
-                double t1, t2, tz;
-                {
-#pragma clang fp contract(off)
-                    t1 = p90 * p.hi;                        // :202
-                    t2 = noise_e + (p90 - noise_e) * p.lo;  // :217
-                    tz = noise_z * p.zr;                    // :247
-                }
-                auto near = [&](double e, double t) {
-                    const double d = fabs(e - t);
-                    return d <= 1e-11 * fmax(fabs(e), fabs(t)) && !(e == 0.0 && t == 0.0);
-                };
+                const VadThresholds th = vad_thresholds(p90, noise_e, noise_z, p);
+                const double t1 = th.t1, t2 = th.t2, tz = th.tz;
                 int nr = 0;
                 int64_t n3 = -1, n4 = -1;
                 for (int64_t q = 0; q < nv; q++)  // :205-213
@@ -336,7 +314,7 @@ __device__ __forceinline__ void general_clip(const Params &p, Sh &s, const Ws &w
                     }
                 if (certify) {  // the decisions of N3 / N4 depend on frames <= N3 and >= N4
                     for (int64_t q = 0; q < nv; q++)
-                        if ((n3 < 0 || q <= n3 || q >= n4) && near(w.vE[q], t1)) nr = 1;
+                        if ((n3 < 0 || q <= n3 || q >= n4) && near_tie(w.vE[q], t1)) nr = 1;
                 }
                 int64_t n1 = 0, n6 = nv - 1;
                 if (n3 >= 0) {
@@ -353,7 +331,7 @@ __device__ __forceinline__ void general_clip(const Params &p, Sh &s, const Ws &w
                         }
                     if (certify)
                         for (int64_t q = 0; q < nv; q++)
-                            if (((q >= n2 - 1 && q < n3) || (q > n4 && q <= n5 + 1)) && near(w.vE[q], t2)) nr = 1;
+                            if (((q >= n2 - 1 && q < n3) || (q > n4 && q <= n5 + 1)) && near_tie(w.vE[q], t2)) nr = 1;
                     for (int64_t q = n2 - 1; q >= 0; q--)  // :249-256
                         if ((double)w.vZ[q] <= tz) {
                             n1 = q + 1;

@@ -235,6 +235,48 @@ def test_near_tie_redo_exact():
             assert out["status"][0] & 0x100, out["status"]
 
 
+def test_near_tie_redo_same_under_either_layout():
+    """The one exact-redo kernel always works in the runtime LDS layout, after a FAST launch too: a
+    near tie redone after a FAST launch, after a launch in the runtime layout (max_len past the
+    compile-time layout's capacity) and by dsp_extract_general gives the same bits, and the oracle's
+    result.  At (1000, 400) every VAD frame inside near_tie_clip's period-4 opening holds exactly
+    L / 2 nonzero samples: energy p90 / 2 = T1, the tie test_near_tie_redo_exact asserts."""
+    import torch
+    import edge_corpus as ec
+    from src.pipeline import FeatureExtractor, create_window
+    from src.synth import make_clip
+    from test_gpu_general import _general
+    from test_gpu_production import near_tie_clip
+    L, S = 1000, 400
+    clips = [near_tie_clip(), make_clip(71, 44100)]
+    off = np.zeros(len(clips) + 1, np.int64)
+    off[1:] = np.cumsum([c.size for c in clips])
+    pcm = np.concatenate(clips + [np.zeros(16, np.int16)])
+    fx = FeatureExtractor(L, S, "hamming", True)
+    longest = max(c.size for c in clips)
+    max_len = ec.fast_cap(L, S) + 1
+    assert ec.fast_layout(longest, L, S) == 1
+    assert max_len >= longest and ec.fast_layout(max_len, L, S) == 0 and ec.lds_bytes(max_len, L, S) > 0
+    t = torch.as_tensor(pcm).cuda()
+    runs = {"fast": {k: v.cpu().numpy().copy() for k, v in fx(t, off).items()},
+            "runtime": {k: v.cpu().numpy().copy() for k, v in fx(t, off, max_len=max_len).items()},
+            "general": _general(pcm, off, L, S, "hamming", True)}
+    for name in ("fast", "runtime"):
+        assert runs[name]["status"][0] & 0x100, (name, runs[name]["status"])
+    w = create_window("hamming", L)
+    refs = [oracle.process_clip(c, L, S, w, do_vad=True) for c in clips]
+    a = runs["fast"]
+    for name, out in runs.items():
+        for k in ("feat", "start_end", "n_frames"):
+            assert np.array_equal(np.ascontiguousarray(out[k]).view(np.uint32),
+                                  np.ascontiguousarray(a[k]).view(np.uint32)), (name, k, out[k], a[k])
+        for i, r in enumerate(refs):
+            assert (out["status"][i] & 0xFF) == r["status"] == 0, (name, i)
+            assert tuple(out["start_end"][i]) == (r["start"], r["end"]), (name, i)
+            assert out["n_frames"][i] == r["n_frames"], (name, i)
+            assert not feat_close(out["feat"][i], r["feat"]).any(), (name, i, out["feat"][i], r["feat"])
+
+
 def test_absolute_term_only_near_zero(golden, packed):
     """The 15-d check adds 1e-6 x |group mean| to the 1e-5 relative tolerance (feat_close).  Count
     the cells that pass only through that term -- over every golden configuration and a random

@@ -1,5 +1,6 @@
-"""Static instruction counts of extract_kernel per source-line range (phase), from the gfx950 ISA
-with line tables:  python tools/isa_phases.py [asm]  (default: builds /tmp/extract_g.s)."""
+"""Static instruction counts of extract_kernel per source-line range (phase) of clip_fast in
+extract.hip (the runtime layout's clip_body lives in extract_generic.h and is not broken down), from
+the gfx950 ISA with line tables:  python tools/isa_phases.py [asm]  (default: builds /tmp/extract_g.s)."""
 import collections, os, re, subprocess, sys
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CS = os.path.join(R, "dsp-audioreclabs_amd", "csrc")
@@ -8,7 +9,7 @@ if len(sys.argv) == 1:
     subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "-I" + os.path.join(R, "include"), "-I" + CS,
                     "--offload-device-only", "-gline-tables-only", "-S", os.path.join(CS, "extract.hip"), "-o", asm], check=True)
 src = open(os.path.join(CS, "extract.hip")).read().split("\n")
-body = ([i + 1 for i, l in enumerate(src) if "bool clip_body(" in l][0],
+body = ([i + 1 for i, l in enumerate(src) if "bool clip_fast(" in l][0],  # (clip_body: extract_generic.h)
         [i + 1 for i, l in enumerate(src) if "void write_bad_clip(" in l][0])
 marks = [(i + 1, l.strip()) for i, l in enumerate(src) if re.match(r"\s*// ---- R\d", l) or "STAMP(i," in l]
 def phase(line):
@@ -27,7 +28,7 @@ for l in open(asm).read().split("\n"):
     if m: fn = m.group(1)
     m = re.match(r"\s*\.loc\s+(\d+)\s+(\d+)", l)
     if m:
-        # innermost location of the inlining chain that lies inside clip_body
+        # innermost location of the inlining chain that lies inside clip_fast
         chain = [int(x) for x in re.findall(r"extract\.hip:(\d+)", l)]
         inside = [x for x in chain if body[0] <= x <= body[1]]
         if inside: cur = inside[0]
