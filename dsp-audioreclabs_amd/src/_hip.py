@@ -34,7 +34,8 @@ EXPORTS = ("dsp_extract_lds_bytes", "dsp_extract_fast_layout", "dsp_extract_feat
            "dsp_extract_general", "dsp_knn_workspace_bytes", "dsp_knn_workspace_fallbacks_offset",
            "dsp_knn_classify", "dsp_zscore_fit", "dsp_zscore_apply", "dsp_wav_scan", "dsp_wav_read",
            "dsp_abi_version", "dsp_mlp_lds_bytes", "dsp_mlp_param_count", "dsp_mlp_train",
-           "dsp_mlp_predict", "dsp_mlp_dropout_mask")
+           "dsp_mlp_predict", "dsp_mlp_dropout_mask", "dsp_svc_workspace_bytes",
+           "dsp_svc_workspace_uncertified_offset", "dsp_svc_launch_parts", "dsp_svc_predict")
 DSP_WAV_OTHER, DSP_WAV_S16_MONO, DSP_WAV_U8_MONO = 0, 1, 2
 
 _lib = None
@@ -112,6 +113,15 @@ def load_library(path=LIB_PATH):
         L.dsp_mlp_predict.argtypes = [vp, vp, i64, i32, i32, vp, i32, vp, vp, vp]
         L.dsp_mlp_dropout_mask.restype = i32
         L.dsp_mlp_dropout_mask.argtypes = [u32, i64, i32, i32, i32, u32, vp, vp]
+    if hasattr(L, "dsp_svc_predict"):  # (older A/B variants lack the SVC)
+        L.dsp_svc_workspace_bytes.restype = sz
+        L.dsp_svc_workspace_bytes.argtypes = [i64, i64, i32, i32]
+        L.dsp_svc_workspace_uncertified_offset.restype = sz
+        L.dsp_svc_workspace_uncertified_offset.argtypes = [i64, i64, i32, i32]
+        L.dsp_svc_launch_parts.restype = i32
+        L.dsp_svc_launch_parts.argtypes = [i64, i64, i32, i32]
+        L.dsp_svc_predict.restype = i32
+        L.dsp_svc_predict.argtypes = [vp, vp, vp, vp, i64, i32, i32, dbl, vp, i64, vp, vp, vp, vp, sz, vp]
     _lib = L
     return L
 

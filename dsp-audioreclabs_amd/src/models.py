@@ -3,10 +3,19 @@
 ``TraditionalClassifier('knn')`` (models.py:18-72) -- the classifier on the north-star path --
 runs the exact k-NN kernel (csrc/knn.hip, dsp_knn_classify): the same neighbours, distances and
 majority vote as scikit-learn's KNeighborsClassifier(n_neighbors=k) (kd_tree, Euclidean,
-uniform weights, scipy.stats.mode: smallest label on ties).  The other classifier types of the
-reference (naive_bayes, decision_tree, svm) are not part of the accelerated path (SURVEY.md §8,
-DESIGN.md §7); they keep the reference's scikit-learn models so a caller switching over loses
-nothing.
+uniform weights, scipy.stats.mode: smallest label on ties).
+
+``TraditionalClassifier('svm')`` trains with scikit-learn's SVC (libsvm) exactly as the reference
+does -- a device SMO would converge to another dual solution -- and predicts the
+fitted RBF model on the device (csrc/svm.hip, dsp_svc_predict): libsvm's kernel
+sums and one-vs-one vote in fp64, each row certified against a derived rounding bound and the few
+uncertifiable rows answered by libsvm itself, so the labels are SVC.predict's.  Other kernels
+(linear, poly, sigmoid), sparse input and models outside the kernel's plan predict through
+scikit-learn as before.
+
+The remaining classifier types of the reference (naive_bayes, decision_tree) are not part of the
+accelerated path; they keep the reference's scikit-learn models so a
+caller switching over loses nothing.
 
 ``MLPTrainer`` (models.py:109-221) trains the reference's MLP with the fused on-device trainer
 (csrc/mlp.hip: dsp_mlp_train / dsp_mlp_predict) -- the whole serial SGD loop of
@@ -16,7 +25,7 @@ learning-rate sweep in one launch.
 """
 import numpy as np
 
-from .pipeline import KnnIndex
+from .pipeline import KnnIndex, SvcIndex
 
 
 class TraditionalClassifier:
@@ -36,12 +45,18 @@ class TraditionalClassifier:
         elif classifier_type == 'svm':
             from sklearn.svm import SVC
             self.model = SVC(C=kwargs.get('C', 1.0), kernel=kwargs.get('kernel', 'rbf'), random_state=42)
+            self._svc_index = None
+            # which path the last predict / decision_function took (device: dsp_svc_predict ran;
+            # uncertified: rows of it answered by libsvm)
+            self.last_predict_stats = {'device': False, 'uncertified': 0}
         else:
             raise ValueError(f"不支持的分类器类型: {classifier_type}")
 
     def fit(self, X_train, y_train):
         if self.classifier_type != 'knn':
             self.model.fit(X_train, y_train)
+            if self.classifier_type == 'svm':
+                self._svc_index = None  # the fitted model is uploaded at the first predict
             return self
         X = np.asarray(X_train, dtype=np.float64)
         y = np.asarray(y_train)
@@ -60,8 +75,49 @@ class TraditionalClassifier:
         idx, dist, _ = self._index.query(np.asarray(X_test, dtype=np.float64))
         return dist.cpu().numpy(), idx.cpu().numpy().astype(np.int64)
 
+    # -- SVC prediction on the device (models.py:56-58 with the model of :44-47) ---------------
+    def _svc_on_device(self, X):
+        """The fitted model is an RBF SVC inside dsp_svc_predict's plan and X is dense."""
+        from scipy.sparse import issparse
+        m = self.model
+        n_classes = len(getattr(m, 'classes_', ()))
+        return (m.kernel == 'rbf' and not m.probability and not m.break_ties and not getattr(m, '_sparse', False)
+                and not issparse(X) and 2 <= n_classes <= 64 and 1 <= m.support_vectors_.shape[1] <= 4096)
+
+    def _svc_query(self, X, with_dec):
+        """(pred, dec, certified) as numpy arrays from the device, and the stats record."""
+        # uploaded once per fitted model (a refit, also one made on self.model directly, replaces
+        # the support vector array)
+        if self._svc_index is None or self._svc_index.source is not self.model.support_vectors_:
+            self._svc_index = SvcIndex(self.model)
+        X = np.asarray(X, dtype=np.float64)
+        stats = {}
+        pred, dec, cert = self._svc_index.query(X, with_dec=with_dec, stats=stats)
+        self.last_predict_stats = {'device': True, 'uncertified': int(stats.get('uncertified', 0))}
+        return X, pred.cpu().numpy(), dec.cpu().numpy() if with_dec else None, cert.cpu().numpy()
+
+    def decision_function(self, X):
+        """SVC.decision_function with decision_function_shape='ovo' ([n, C(C-1)/2]; [n] and
+        scikit-learn's flipped sign for two classes).  SVM only."""
+        if self.classifier_type != 'svm':
+            raise AttributeError("decision_function is the SVM's")
+        if not self._svc_on_device(X):
+            self.last_predict_stats = {'device': False, 'uncertified': 0}
+            return self.model._decision_function(X)
+        _, _, dec, _ = self._svc_query(X, True)
+        return -dec.ravel() if dec.shape[1] == 1 else dec
+
     def predict(self, X_test):
+        if self.classifier_type == 'svm' and self._svc_on_device(X_test):
+            X, pred, _, cert = self._svc_query(X_test, False)
+            y = self.model.classes_[pred]
+            redo = np.flatnonzero(cert == 0)
+            if len(redo):  # near ties the rounding bound cannot decide: libsvm's own answer
+                y[redo] = self.model.predict(X[redo])
+            return y
         if self.classifier_type != 'knn':
+            if self.classifier_type == 'svm':
+                self.last_predict_stats = {'device': False, 'uncertified': 0}
             return self.model.predict(X_test)
         _, _, pred = self._index.query(np.asarray(X_test, dtype=np.float64))
         return self.classes_[pred.cpu().numpy()]

@@ -249,6 +249,69 @@ def knn_classify(ref, ref_labels, query, k, self_offset=-1, n_classes=None, with
     return KnnIndex(ref, ref_labels, k, n_classes, with_pred).query(query, self_offset, stats)
 
 
+class SvcIndex:
+    """A fitted ``sklearn.svm.SVC(kernel='rbf')`` uploaded once for ``dsp_svc_predict``
+    (csrc/svm.hip): libsvm's own arrays -- support_vectors_, _n_support, _dual_coef_, _intercept_,
+    _gamma (the underscore attributes: the public ones are sign-flipped for two classes).
+    ``query`` is SVC.predict's vote as class indices plus, per row, whether the device could certify
+    it; the caller answers uncertified rows with the model itself.  One query at a
+    time per index (the workspace is a launch's scratch)."""
+
+    WORKSPACE_CAP = 256 << 20  # a query batch is cut into launches whose scratch stays below this
+
+    def __init__(self, model):
+        import torch
+        self.device = _hip.require_device()
+        self.source = model.support_vectors_  # the array this index was uploaded from
+        sv = np.asarray(self.source, dtype=np.float64)
+        self.nSV, self.D = sv.shape
+        self.C = len(model.classes_)
+        self.P = self.C * (self.C - 1) // 2
+        self.gamma = float(model._gamma)
+        if _hip.lib().dsp_svc_workspace_bytes(self.nSV, 1, self.D, self.C) == 0:
+            raise ValueError("SVC outside the device plan (1 <= D <= 4096, 2 <= classes <= 64)")
+        self.sv = _as_device(sv, torch.float64, self.device)
+        self.n_support = _as_device(model._n_support, torch.int32, self.device)
+        self.dual_coef = _as_device(np.asarray(model._dual_coef_, dtype=np.float64).reshape(self.C - 1, self.nSV),
+                                    torch.float64, self.device)
+        self.intercept = _as_device(np.asarray(model._intercept_, dtype=np.float64).reshape(self.P),
+                                    torch.float64, self.device)
+        self._ws = None
+
+    def query(self, X, with_dec=False, stats=None):
+        """(pred int32 [Nq] class index, dec float64 [Nq, C(C-1)/2] with libsvm's signs or None,
+        certified int32 [Nq]); a dict passed as ``stats`` receives "uncertified" (one host sync)."""
+        import torch
+        d, L = self.device, _hip.lib()
+        q = _as_device(X, torch.float64, d)
+        if q.dim() != 2 or q.shape[1] != self.D:
+            raise ValueError("X has shape %s, the model was fitted on %d features" % (tuple(q.shape), self.D))
+        Nq = q.shape[0]
+        pred = torch.empty(Nq, dtype=torch.int32, device=d)
+        cert = torch.empty(Nq, dtype=torch.int32, device=d)
+        dec = torch.empty((Nq, self.P), dtype=torch.float64, device=d) if with_dec else None
+        # rows per launch: the scratch of a launch is (C (C-1) + C) doubles per row and part
+        step = max(1024, self.WORKSPACE_CAP // (8 * self.C * self.C))
+        uncertified = 0
+        for lo in range(0, Nq, step):
+            n = min(step, Nq - lo)
+            ws_bytes = L.dsp_svc_workspace_bytes(self.nSV, n, self.D, self.C)
+            if self._ws is None or self._ws.numel() < ws_bytes:
+                self._ws = torch.empty(ws_bytes, dtype=torch.uint8, device=d)
+            rc = L.dsp_svc_predict(_hip.ptr(self.sv), _hip.ptr(self.n_support), _hip.ptr(self.dual_coef),
+                                   _hip.ptr(self.intercept), self.nSV, self.D, self.C, self.gamma,
+                                   _hip.ptr(q[lo:lo + n]), n, _hip.ptr(pred[lo:lo + n]),
+                                   _hip.ptr(dec[lo:lo + n]) if with_dec else None, _hip.ptr(cert[lo:lo + n]),
+                                   _hip.ptr(self._ws), self._ws.numel(), _hip.stream_handle(d))
+            _hip.check(rc, "dsp_svc_predict")
+            if stats is not None:
+                off = L.dsp_svc_workspace_uncertified_offset(self.nSV, n, self.D, self.C)
+                uncertified += int(self._ws[off:off + 4].view(torch.int32).item())
+        if stats is not None:
+            stats["uncertified"] = uncertified
+        return pred, dec, cert
+
+
 def zscore_fit(X):
     """normalize_features' mean/std (src/feature_extraction.py:171-177) on the device."""
     import torch

@@ -36,7 +36,7 @@ extern "C" {
                               5: queue_ws is 4 KiB (each counter on its own 256-B line);
                               6: the extraction entry points take out_stride (packed result rows);
                                  dsp_knn_classify takes flags (DSP_KNN_REF_READY).
-                              Still 6 with the dsp_mlp_* entry points: they are new symbols only, no
+                              Still 6 with the dsp_mlp_* and dsp_svc_* entry points: they are new symbols only, no
                               existing signature or meaning changed, so callers built against 6 keep
                               working (a binding that needs them checks for the symbols) */
 
@@ -273,6 +273,47 @@ int dsp_mlp_predict(const float *params, const float *X, int64_t Nq, int D, int 
  * function (nn.Dropout's mask, src/models.py:97). */
 int dsp_mlp_dropout_mask(uint32_t seed, int64_t step, int layer, int rows, int width,
                          uint32_t drop_threshold, uint8_t *mask, void *stream);
+
+/*
+ * SVC prediction -- SVC(kernel='rbf').predict of a model fitted by scikit-learn (libsvm), as
+ * configured in src/models.py:44-47 and used by TraditionalClassifier.predict / evaluate (:56-58).
+ * Training stays libsvm's; the fitted model is passed as libsvm holds it (scikit-learn's underscore
+ * attributes -- the public dual_coef_ / intercept_ are sign-flipped for two classes):
+ *   sv         float64 [nSV, D]     support_vectors_, grouped by class
+ *   n_support  int32   [C]          _n_support (rows of sv per class, summing to nSV)
+ *   dual_coef  float64 [C-1, nSV]   _dual_coef_
+ *   intercept  float64 [C(C-1)/2]   _intercept_ (= -rho), in libsvm's pair order p: (0,1), (0,2), ...
+ *   gamma                            _gamma
+ * For each row of query float64 [Nq, D]:
+ *   K_s   = exp(-gamma * sum_d (q_d - sv[s][d])^2)            (the direct form, fp64)
+ *   dec_p = sum_{s in class i} dual_coef[j-1][s] K_s + sum_{s in class j} dual_coef[i][s] K_s
+ *           + intercept[p]                                     for the pair i < j
+ *   a vote for i if dec_p > 0, else for j; pred = the first class index with the most votes
+ *   (SVC.predict is classes_[pred]).
+ * dec        float64 [Nq, C(C-1)/2] with libsvm's signs, or NULL.  For C > 2 this is
+ *            decision_function with decision_function_shape='ovo'; for C == 2 its negation.
+ * certified  int32 [Nq]: 1 when every |dec_p| exceeds four times the derived bound on
+ *            |dec_device - dec_libsvm| (any summation order on both sides, a few ulp per exp, the
+ *            rounding of the squared distance), so the vote is libsvm's; 0: the
+ *            caller answers that row with libsvm itself.  Equal inputs give equal bits, and a row's
+ *            dec bits do not depend on Nq or on the row's position (fixed summation order, no atomics
+ *            on floating-point data).
+ * workspace  device scratch of dsp_svc_workspace_bytes(nSV, Nq, D, C) bytes (0: sizes outside the
+ *            plan); at dsp_svc_workspace_uncertified_offset an int32 is left holding the number of
+ *            uncertified rows.
+ * dsp_svc_launch_parts (diagnostic, host only): 1 when a call of these sizes runs the query-tiled
+ *            launch (a workgroup walks all support vectors), else the number of support-vector
+ *            segments the launch is split over (few queries against many support vectors).
+ * Requires 1 <= D <= 4096 (D <= 32: the query in registers, else dimensions in chunks of 16),
+ * 2 <= C <= 64, 1 <= nSV < 2^31, gamma >= 0.
+ */
+size_t dsp_svc_workspace_bytes(int64_t nSV, int64_t Nq, int D, int C);
+size_t dsp_svc_workspace_uncertified_offset(int64_t nSV, int64_t Nq, int D, int C);
+int dsp_svc_launch_parts(int64_t nSV, int64_t Nq, int D, int C);
+int dsp_svc_predict(const double *sv, const int32_t *n_support, const double *dual_coef,
+                    const double *intercept, int64_t nSV, int D, int C, double gamma,
+                    const double *query, int64_t Nq, int32_t *pred, double *dec, int32_t *certified,
+                    void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * Batch WAV reader -- host only (no GPU, no stream): the file side of load_wav
