@@ -5,8 +5,8 @@ sub-directory name, files in glob order, errored files skipped: run_experiments.
 decodes every WAV once (src/dataset.PCMDataset: host threads, one pinned upload) and extracts all
 of them in one fused kernel launch per window type instead of one Python loop iteration per
 file; the window comparison reuses the HBM-resident PCM.  ``experiment_classifier_comparison`` /
-``experiment_window_comparison`` follow :249-393 with the KNN on the device and the other
-scikit-learn classifiers unchanged.  The reference's 'MLP' row (:284, :365) is opt-in
+``experiment_window_comparison`` follow :249-393 with the KNN on the device and the scikit-learn
+classifiers' prediction there too (src/models.py; their models are scikit-learn's own).  The reference's 'MLP' row (:284, :365) is opt-in
 (``with_mlp=True``, ``run.py --with-mlp``): the fused on-device trainer with config.MLP_* as in
 :227-236, the window comparison's three MLPs in one launch when the three splits have one shape.
 Plots (src/visualization.py) are out of scope; results are written as JSON, with the reference's

@@ -35,7 +35,9 @@ EXPORTS = ("dsp_extract_lds_bytes", "dsp_extract_fast_layout", "dsp_extract_feat
            "dsp_knn_classify", "dsp_zscore_fit", "dsp_zscore_apply", "dsp_wav_scan", "dsp_wav_read",
            "dsp_abi_version", "dsp_mlp_lds_bytes", "dsp_mlp_param_count", "dsp_mlp_train",
            "dsp_mlp_predict", "dsp_mlp_dropout_mask", "dsp_svc_workspace_bytes",
-           "dsp_svc_workspace_uncertified_offset", "dsp_svc_launch_parts", "dsp_svc_predict")
+           "dsp_svc_workspace_uncertified_offset", "dsp_svc_launch_parts", "dsp_svc_predict",
+           "dsp_gnb_fit", "dsp_gnb_workspace_bytes", "dsp_gnb_predict", "dsp_tree_workspace_bytes",
+           "dsp_tree_lds_nodes", "dsp_tree_predict")
 DSP_WAV_OTHER, DSP_WAV_S16_MONO, DSP_WAV_U8_MONO = 0, 1, 2
 
 _lib = None
@@ -122,6 +124,19 @@ def load_library(path=LIB_PATH):
         L.dsp_svc_launch_parts.argtypes = [i64, i64, i32, i32]
         L.dsp_svc_predict.restype = i32
         L.dsp_svc_predict.argtypes = [vp, vp, vp, vp, i64, i32, i32, dbl, vp, i64, vp, vp, vp, vp, sz, vp]
+    if hasattr(L, "dsp_gnb_predict"):  # (older A/B variants lack Naive Bayes and the tree)
+        L.dsp_gnb_fit.restype = i32
+        L.dsp_gnb_fit.argtypes = [vp, vp, i64, i32, i32, dbl, vp, vp, vp, vp, vp, sz, vp]
+        L.dsp_gnb_workspace_bytes.restype = sz
+        L.dsp_gnb_workspace_bytes.argtypes = [i64, i32, i32]
+        L.dsp_gnb_predict.restype = i32
+        L.dsp_gnb_predict.argtypes = [vp, vp, vp, vp, i32, i32, vp, i64, vp, vp, vp, vp, sz, vp]
+        L.dsp_tree_workspace_bytes.restype = sz
+        L.dsp_tree_workspace_bytes.argtypes = [i64]
+        L.dsp_tree_lds_nodes.restype = i32
+        L.dsp_tree_lds_nodes.argtypes = []
+        L.dsp_tree_predict.restype = i32
+        L.dsp_tree_predict.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, vp, i64, vp, vp, vp, sz, vp]
     _lib = L
     return L
 

@@ -13,9 +13,18 @@ uncertifiable rows answered by libsvm itself, so the labels are SVC.predict's.  
 (linear, poly, sigmoid), sparse input and models outside the kernel's plan predict through
 scikit-learn as before.
 
-The remaining classifier types of the reference (naive_bayes, decision_tree) are not part of the
-accelerated path; they keep the reference's scikit-learn models so a
-caller switching over loses nothing.
+``TraditionalClassifier('naive_bayes')`` keeps a complete scikit-learn ``GaussianNB`` in ``.model``
+and predicts it on the device (csrc/gnb.hip, dsp_gnb_predict): the joint log
+likelihood in fp64, each row's argmax certified against a derived rounding bound, uncertified rows
+answered by GaussianNB.predict.  ``fit`` on a float64 device tensor runs dsp_gnb_fit -- numpy's own
+sequential sums, so theta_, var_, epsilon_ and class_prior_ are GaussianNB.fit's bits -- and with
+host rows it is scikit-learn's fit.
+
+``TraditionalClassifier('decision_tree')`` trains with scikit-learn (the best-split search draws
+its feature order from scikit-learn's RNG and breaks ties by visiting order) and
+walks the fitted tree on the device (csrc/tree.hip, dsp_tree_predict): comparisons only, so
+``predict`` and ``apply`` are scikit-learn's with no tolerance.  Models outside the kernels' plans
+(sparse input, more than 64 classes, multi-output trees) predict through scikit-learn as before.
 
 ``MLPTrainer`` (models.py:109-221) trains the reference's MLP with the fused on-device trainer
 (csrc/mlp.hip: dsp_mlp_train / dsp_mlp_predict) -- the whole serial SGD loop of
@@ -25,7 +34,12 @@ learning-rate sweep in one launch.
 """
 import numpy as np
 
-from .pipeline import KnnIndex, SvcIndex
+from .pipeline import GnbIndex, KnnIndex, SvcIndex, TreeIndex, gaussian_nb_fit
+
+
+def _is_device_f64(X):
+    import torch
+    return isinstance(X, torch.Tensor) and X.is_cuda and X.dtype == torch.float64
 
 
 class TraditionalClassifier:
@@ -39,9 +53,14 @@ class TraditionalClassifier:
         elif classifier_type == 'naive_bayes':
             from sklearn.naive_bayes import GaussianNB
             self.model = GaussianNB()
+            self._index = None
+            self.last_predict_stats = {'device': False, 'uncertified': 0}
         elif classifier_type == 'decision_tree':
             from sklearn.tree import DecisionTreeClassifier
             self.model = DecisionTreeClassifier(max_depth=kwargs.get('max_depth', None), random_state=42)
+            self._index = None
+            # uncertified: rows the device left unanswered (a NaN, or not finite as float32)
+            self.last_predict_stats = {'device': False, 'uncertified': 0}
         elif classifier_type == 'svm':
             from sklearn.svm import SVC
             self.model = SVC(C=kwargs.get('C', 1.0), kernel=kwargs.get('kernel', 'rbf'), random_state=42)
@@ -54,6 +73,8 @@ class TraditionalClassifier:
 
     def fit(self, X_train, y_train):
         if self.classifier_type != 'knn':
+            if self.classifier_type == 'naive_bayes' and _is_device_f64(X_train):
+                return self._fit_nb_device(X_train, y_train)
             self.model.fit(X_train, y_train)
             if self.classifier_type == 'svm':
                 self._svc_index = None  # the fitted model is uploaded at the first predict
@@ -107,7 +128,77 @@ class TraditionalClassifier:
         _, _, dec, _ = self._svc_query(X, True)
         return -dec.ravel() if dec.shape[1] == 1 else dec
 
+    # -- Naive Bayes and Decision Tree on the device (models.py:37-43, :52-58) -----------------
+    def _fit_nb_device(self, X, y):
+        """GaussianNB.fit of device rows with dsp_gnb_fit; .model ends up a complete GaussianNB."""
+        m = self.model
+        y = y.cpu().numpy() if hasattr(y, 'cpu') else np.asarray(y)
+        classes, codes = np.unique(y, return_inverse=True)
+        if X.dim() != 2 or X.shape[1] < 2 or len(classes) > 64 or m.priors is not None or len(y) != X.shape[0]:
+            m.fit(X.cpu().numpy(), y)  # outside dsp_gnb_fit's plan (one column: numpy sums pairwise)
+            return self
+        theta, var, count, eps = gaussian_nb_fit(X, codes.astype(np.int32), len(classes), m.var_smoothing)
+        m.classes_, m.n_features_in_ = classes, int(X.shape[1])
+        m.epsilon_ = np.float64(eps.item())
+        m.theta_, m.var_ = theta.cpu().numpy(), var.cpu().numpy()
+        m.class_count_ = count.cpu().numpy().astype(np.float64)
+        m.class_prior_ = m.class_count_ / m.class_count_.sum()
+        return self
+
+    def _on_device(self, X):
+        """The fitted model is inside dsp_gnb_predict's / dsp_tree_predict's plan and X is dense."""
+        from scipy.sparse import issparse
+        m = self.model
+        if issparse(X):
+            return False
+        if self.classifier_type == 'naive_bayes':
+            theta = getattr(m, 'theta_', None)
+            return theta is not None and 1 <= theta.shape[1] <= 4096 and 1 <= theta.shape[0] <= 64
+        return (getattr(m, 'tree_', None) is not None and m.n_outputs_ == 1 and 1 <= m.n_features_in_ <= 4096)
+
+    def _device_labels(self, X, want_leaf=False):
+        """predict (or apply) of a Naive Bayes / Decision Tree model: the device's answer, and the
+        model's own for the rows the device did not certify or answer."""
+        m = self.model
+        nb = self.classifier_type == 'naive_bayes'
+        source = m.theta_ if nb else m.tree_
+        # uploaded once per fitted model (a refit, also one made on self.model directly, replaces
+        # theta_ / tree_)
+        if self._index is None or self._index.source is not source:
+            self._index = GnbIndex(m) if nb else TreeIndex(m)
+        if not hasattr(X, 'cpu'):
+            X = np.asarray(X, dtype=np.float64)
+        stats = {}
+        if nb:
+            pred, _, cert = self._index.query(X, stats=stats)
+            pred, redo = pred.cpu().numpy(), np.flatnonzero(cert.cpu().numpy() == 0)
+            n = stats['uncertified']
+        else:
+            pred, leaf = self._index.query(X, with_leaf=want_leaf, stats=stats)
+            pred = pred.cpu().numpy()
+            redo, n = np.flatnonzero(pred < 0), stats['unanswered']
+        self.last_predict_stats = {'device': True, 'uncertified': int(n)}
+        out = leaf.cpu().numpy().astype(np.int64) if want_leaf else m.classes_[np.maximum(pred, 0)]
+        if len(redo):  # near ties the bound cannot decide; rows with a NaN or an infinity (it may raise)
+            rows = X[redo].cpu().numpy() if hasattr(X, 'cpu') else X[redo]
+            out[redo] = m.apply(rows) if want_leaf else m.predict(rows)
+        return out
+
+    def apply(self, X):
+        """DecisionTreeClassifier.apply: the leaf's node index per row, int64.  Decision tree only."""
+        if self.classifier_type != 'decision_tree':
+            raise AttributeError("apply is the decision tree's")
+        if not self._on_device(X):
+            self.last_predict_stats = {'device': False, 'uncertified': 0}
+            return self.model.apply(X)
+        return self._device_labels(X, want_leaf=True)
+
     def predict(self, X_test):
+        if self.classifier_type in ('naive_bayes', 'decision_tree'):
+            if self._on_device(X_test):
+                return self._device_labels(X_test)
+            self.last_predict_stats = {'device': False, 'uncertified': 0}
+            return self.model.predict(X_test)
         if self.classifier_type == 'svm' and self._svc_on_device(X_test):
             X, pred, _, cert = self._svc_query(X_test, False)
             y = self.model.classes_[pred]

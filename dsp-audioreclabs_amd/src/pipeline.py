@@ -312,6 +312,136 @@ class SvcIndex:
         return pred, dec, cert
 
 
+def gaussian_nb_fit(X, y_codes, n_classes, var_smoothing=1e-9):
+    """``GaussianNB(var_smoothing=...).fit`` on the device (csrc/gnb.hip, dsp_gnb_fit): X float64
+    [N, D] (D >= 2) and class codes in [0, n_classes).  Returns device tensors (theta [C, D],
+    var [C, D] with epsilon added, class_count int64 [C], epsilon [1]) -- numpy's bits."""
+    import torch
+    d = _hip.require_device()
+    X = _as_device(X, torch.float64, d)
+    y = _as_device(y_codes, torch.int32, d)
+    if X.dim() != 2 or y.shape != (X.shape[0],):
+        raise ValueError("X must be [N, D] and y_codes [N]")
+    N, D = X.shape
+    C = int(n_classes)
+    theta = torch.empty((C, D), dtype=torch.float64, device=d)
+    var = torch.empty((C, D), dtype=torch.float64, device=d)
+    count = torch.empty(C, dtype=torch.int64, device=d)
+    eps = torch.empty(1, dtype=torch.float64, device=d)
+    ws = torch.empty(max(D, 1) * 8, dtype=torch.uint8, device=d)
+    _hip.check(_hip.lib().dsp_gnb_fit(_hip.ptr(X), _hip.ptr(y), N, D, C, float(var_smoothing), _hip.ptr(theta),
+                                      _hip.ptr(var), _hip.ptr(count), _hip.ptr(eps), _hip.ptr(ws), ws.numel(),
+                                      _hip.stream_handle(d)), "dsp_gnb_fit")
+    return theta, var, count, eps
+
+
+class GnbIndex:
+    """A fitted ``sklearn.naive_bayes.GaussianNB`` uploaded once for ``dsp_gnb_predict``
+    (csrc/gnb.hip): theta_, var_ and the two per-class constants of _joint_log_likelihood, computed
+    here with numpy exactly as scikit-learn does.  ``query`` is GaussianNB.predict's argmax as class
+    indices plus, per row, whether the device could certify it; the caller answers
+    uncertified rows with the model itself.  One query at a time per index."""
+
+    WORKSPACE_CAP = 256 << 20  # a query batch is cut into launches whose scratch stays below this
+
+    def __init__(self, model):
+        import torch
+        self.device = _hip.require_device()
+        self.source = model.theta_  # the array this index was uploaded from
+        theta = np.asarray(model.theta_, dtype=np.float64)
+        var = np.asarray(model.var_, dtype=np.float64)
+        self.C, self.D = theta.shape
+        if _hip.lib().dsp_gnb_workspace_bytes(1, self.D, self.C) == 0:
+            raise ValueError("GaussianNB outside the device plan (1 <= D <= 4096, 1 <= classes <= 64)")
+        with np.errstate(divide='ignore'):
+            log_prior = np.log(np.asarray(model.class_prior_, dtype=np.float64))
+        nconst = -0.5 * np.sum(np.log(2.0 * np.pi * var), axis=1)
+        self.theta = _as_device(theta, torch.float64, self.device)
+        self.var = _as_device(var, torch.float64, self.device)
+        self.log_prior = _as_device(log_prior, torch.float64, self.device)
+        self.nconst = _as_device(nconst, torch.float64, self.device)
+        self._ws = None
+
+    def query(self, X, with_jll=False, stats=None):
+        """(pred int32 [Nq] class index, jll float64 [Nq, C] or None, certified int32 [Nq]); a dict
+        passed as ``stats`` receives "uncertified" (one host sync)."""
+        import torch
+        d, L = self.device, _hip.lib()
+        q = _as_device(X, torch.float64, d)
+        if q.dim() != 2 or q.shape[1] != self.D:
+            raise ValueError("X has shape %s, the model was fitted on %d features" % (tuple(q.shape), self.D))
+        Nq = q.shape[0]
+        pred = torch.empty(Nq, dtype=torch.int32, device=d)
+        cert = torch.empty(Nq, dtype=torch.int32, device=d)
+        jll = torch.empty((Nq, self.C), dtype=torch.float64, device=d) if with_jll else None
+        step = max(1024, self.WORKSPACE_CAP // (16 * self.C))  # a launch's scratch: 2 C doubles per row
+        uncertified = 0
+        for lo in range(0, Nq, step):
+            n = min(step, Nq - lo)
+            ws_bytes = L.dsp_gnb_workspace_bytes(n, self.D, self.C)
+            if self._ws is None or self._ws.numel() < ws_bytes:
+                self._ws = torch.empty(ws_bytes, dtype=torch.uint8, device=d)
+            rc = L.dsp_gnb_predict(_hip.ptr(self.theta), _hip.ptr(self.var), _hip.ptr(self.log_prior),
+                                   _hip.ptr(self.nconst), self.D, self.C, _hip.ptr(q[lo:lo + n]), n,
+                                   _hip.ptr(pred[lo:lo + n]), _hip.ptr(jll[lo:lo + n]) if with_jll else None,
+                                   _hip.ptr(cert[lo:lo + n]), _hip.ptr(self._ws), self._ws.numel(),
+                                   _hip.stream_handle(d))
+            _hip.check(rc, "dsp_gnb_predict")
+            if stats is not None:
+                uncertified += int(self._ws[:4].view(torch.int32).item())
+        if stats is not None:
+            stats["uncertified"] = uncertified
+        return pred, jll, cert
+
+
+class TreeIndex:
+    """A fitted single-output ``sklearn.tree.DecisionTreeClassifier`` uploaded once for
+    ``dsp_tree_predict`` (csrc/tree.hip): tree_'s children, features and thresholds and every
+    node's majority class.  ``query`` is predict (as class indices) and apply; a row with a NaN
+    (scikit-learn's missing value) or a value that is not finite as float32 (scikit-learn refuses
+    it) comes back as -1, for the caller to hand to the model itself.  One query at a
+    time per index."""
+
+    def __init__(self, model):
+        import torch
+        self.device = _hip.require_device()
+        t = model.tree_
+        self.source = t  # the tree this index was uploaded from
+        if model.n_outputs_ != 1:
+            raise ValueError("only single-output trees are inside the device plan")
+        self.n_nodes, self.max_depth, self.D = int(t.node_count), int(t.max_depth), int(model.n_features_in_)
+        ws_bytes = _hip.lib().dsp_tree_workspace_bytes(self.n_nodes)
+        if ws_bytes == 0 or not 1 <= self.D <= 4096:
+            raise ValueError("tree outside the device plan (1 <= D <= 4096, 1 <= nodes < 2^31)")
+        leaf_class = np.argmax(t.value[:, 0, :], axis=1)
+        self.left = _as_device(t.children_left, torch.int32, self.device)
+        self.right = _as_device(t.children_right, torch.int32, self.device)
+        self.feature = _as_device(t.feature, torch.int32, self.device)
+        self.threshold = _as_device(t.threshold, torch.float64, self.device)
+        self.leaf_class = _as_device(leaf_class, torch.int32, self.device)
+        self._ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
+
+    def query(self, X, with_leaf=True, stats=None):
+        """(pred int32 [Nq] class index or -1, leaf int32 [Nq] node index or -1, or None); a dict
+        passed as ``stats`` receives "unanswered" (one host sync)."""
+        import torch
+        d = self.device
+        q = _as_device(X, torch.float64, d)
+        if q.dim() != 2 or q.shape[1] != self.D:
+            raise ValueError("X has shape %s, the model was fitted on %d features" % (tuple(q.shape), self.D))
+        Nq = q.shape[0]
+        pred = torch.empty(Nq, dtype=torch.int32, device=d)
+        leaf = torch.empty(Nq, dtype=torch.int32, device=d) if with_leaf else None
+        rc = _hip.lib().dsp_tree_predict(_hip.ptr(self.left), _hip.ptr(self.right), _hip.ptr(self.feature),
+                                         _hip.ptr(self.threshold), _hip.ptr(self.leaf_class), self.n_nodes,
+                                         self.max_depth, self.D, _hip.ptr(q), Nq, _hip.ptr(pred), _hip.ptr(leaf),
+                                         _hip.ptr(self._ws), self._ws.numel(), _hip.stream_handle(d))
+        _hip.check(rc, "dsp_tree_predict")
+        if stats is not None:
+            stats["unanswered"] = int(self._ws[:4].view(torch.int32).item())
+        return pred, leaf
+
+
 def zscore_fit(X):
     """normalize_features' mean/std (src/feature_extraction.py:171-177) on the device."""
     import torch

@@ -36,7 +36,7 @@ extern "C" {
                               5: queue_ws is 4 KiB (each counter on its own 256-B line);
                               6: the extraction entry points take out_stride (packed result rows);
                                  dsp_knn_classify takes flags (DSP_KNN_REF_READY).
-                              Still 6 with the dsp_mlp_* and dsp_svc_* entry points: they are new symbols only, no
+                              Still 6 with the dsp_mlp_*, dsp_svc_*, dsp_gnb_* and dsp_tree_* entry points: new symbols only, no
                               existing signature or meaning changed, so callers built against 6 keep
                               working (a binding that needs them checks for the symbols) */
 
@@ -314,6 +314,81 @@ int dsp_svc_predict(const double *sv, const int32_t *n_support, const double *du
                     const double *intercept, int64_t nSV, int D, int C, double gamma,
                     const double *query, int64_t Nq, int32_t *pred, double *dec, int32_t *certified,
                     void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Gaussian Naive Bayes -- GaussianNB().fit / .predict as configured in src/models.py:37-39 (no
+ * priors, no sample weights) and used by TraditionalClassifier.fit / predict (:52-58).
+ *
+ * dsp_gnb_fit: X float64 [N, D] and y int32 [N], class codes in [0, C) (the index into classes_).
+ *   theta        float64 [C, D]  theta_: the column sums over the class's rows, added in row order,
+ *                                divided by the class's count
+ *   var          float64 [C, D]  var_: sum (x - theta)^2 in row order, divided by the count, + epsilon
+ *   class_count  int64   [C]     class_count_
+ *   epsilon      float64 [1]     epsilon_ = var_smoothing * the largest all-rows column variance
+ *                                (np.var(X, axis=0).max(), the same two passes over all rows)
+ *   These are numpy's own sequential fp64 chains (axis 0, D >= 2), neither reordered nor atomic:
+ *   the four arrays equal GaussianNB().fit's bit for bit.  class_prior_ is class_count /
+ *   class_count.sum(), the caller's.
+ *   workspace    device scratch of at least 8 D bytes.
+ *   A class without rows gets class_count 0 and NaN in its theta and var rows (0 / 0); a row whose
+ *   code is outside [0, C) counts for epsilon only.
+ *   Requires 2 <= D <= 4096 (D = 1: DSP_ERR_ARGS -- numpy sums that case pairwise), 1 <= C <= 64,
+ *   N >= 1.
+ *
+ * dsp_gnb_predict: theta, var float64 [C, D] (var_ with epsilon, as fitted), log_prior float64 [C]
+ * = np.log(class_prior_), nconst float64 [C] = -0.5 * np.sum(np.log(2 pi var_), axis=1) (the
+ * caller computes both with numpy, as _joint_log_likelihood does).  For each row of X float64 [Nq, D]:
+ *   Q_c   = sum_d (x_d - theta[c][d])^2 / var[c][d]       (fp64, added in column order)
+ *   jll_c = log_prior[c] + (nconst[c] - 0.5 Q_c)
+ *   pred  = the first index of the largest jll (GaussianNB.predict is classes_[pred])
+ * jll        float64 [Nq, C], or NULL.
+ * certified  int32 [Nq]: 1 when every score is finite and jll_pred - jll_c exceeds four times
+ *            (bound_pred + bound_c) for every other class c,
+ *              bound_c = 2 (D + 8) 2^-53 (|log_prior[c]| + |nconst[c]| + Q_c / 2)
+ *            the derived bound on |jll_device - jll_sklearn|, so the label is
+ *            scikit-learn's; 0: the caller answers that row with scikit-learn itself (a row with a
+ *            NaN or an infinity is never certified).  Equal inputs give equal bits, and a row's bits
+ *            do not depend on Nq or on the row's position.
+ * workspace  device scratch of dsp_gnb_workspace_bytes(Nq, D, C) bytes (0: sizes outside the plan);
+ *            its first int32 is left holding the number of uncertified rows.
+ * Requires 1 <= D <= 4096 (D <= 32: the query in registers), 1 <= C <= 64.
+ */
+int dsp_gnb_fit(const double *X, const int32_t *y, int64_t N, int D, int C, double var_smoothing,
+                double *theta, double *var, int64_t *class_count, double *epsilon, void *workspace,
+                size_t workspace_bytes, void *stream);
+size_t dsp_gnb_workspace_bytes(int64_t Nq, int D, int C);
+int dsp_gnb_predict(const double *theta, const double *var, const double *log_prior, const double *nconst,
+                    int D, int C, const double *X, int64_t Nq, int32_t *pred, double *jll,
+                    int32_t *certified, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Decision tree prediction -- DecisionTreeClassifier.predict / .apply of a fitted single-output
+ * tree (src/models.py:40-43, :56-58).  Training stays scikit-learn's.  The tree as tree_ holds it:
+ *   children_left, children_right, feature  int32 [n_nodes]   (children_left == -1: a leaf)
+ *   threshold                               float64 [n_nodes]
+ *   leaf_class                              int32 [n_nodes]   np.argmax(tree_.value[:, 0, :], axis=1)
+ *   max_depth                               tree_.max_depth
+ * For each row of X float64 [Nq, D]: from node 0, v = (double)(float)x[feature] (to nearest even,
+ * scikit-learn's float32 cast), left iff v <= threshold, until a leaf.
+ *   pred  int32 [Nq]  leaf_class of the leaf (predict is classes_[pred])
+ *   leaf  int32 [Nq]  the leaf's node index (apply), or NULL
+ * A row that holds a NaN, or a value that is not finite as float32, gets pred = leaf = -1
+ * (scikit-learn treats a NaN as a missing value and refuses the others: the caller hands the row to
+ * it).  The walk ends on any
+ * table: at most max_depth + 1 nodes are visited, and a child index outside (node, n_nodes) or a
+ * feature index outside [0, D) ends it with pred = leaf = -1.
+ * workspace  device scratch of dsp_tree_workspace_bytes(n_nodes) bytes (the packed 16-byte nodes);
+ *            its first int32 is left holding the number of rows answered -1.
+ * dsp_tree_lds_nodes (host only): up to this many nodes the walk reads the table from LDS, beyond
+ *            it from memory.
+ * Requires 1 <= n_nodes < 2^31, max_depth >= 0, 1 <= D <= 4096.
+ */
+size_t dsp_tree_workspace_bytes(int64_t n_nodes);
+int dsp_tree_lds_nodes(void);
+int dsp_tree_predict(const int32_t *children_left, const int32_t *children_right, const int32_t *feature,
+                     const double *threshold, const int32_t *leaf_class, int64_t n_nodes, int max_depth,
+                     int D, const double *X, int64_t Nq, int32_t *pred, int32_t *leaf, void *workspace,
+                     size_t workspace_bytes, void *stream);
 
 /*
  * Batch WAV reader -- host only (no GPU, no stream): the file side of load_wav
