@@ -5,7 +5,7 @@
 // Fit.  scikit-learn takes np.mean and np.var (axis 0) of each class's rows and np.var of all
 // rows; numpy adds along axis 0 sequentially in row order (D >= 2), so every (class, column) pair
 // and every (all rows, column) pair is one dependent chain of fp64 adds -- (C + 1) D independent
-// chains.  gnb_fit_kernel keeps them fed the way zscore_fit_kernel (knn.hip) does: two waves stage
+// chains.  gnb_fit_kernel keeps them fed the way zscore_fit_kernel (zscore.hip) does: two waves stage
 // tiles of rows and labels in LDS while the lanes of the other two own one (class, column) pair
 // each and add the tile in row order, the add predicated on the label.  No reordering, no atomics:
 // theta, var, epsilon are numpy's bits.  gnb_fit_finish takes the largest all-rows variance and

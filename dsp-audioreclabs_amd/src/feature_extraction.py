@@ -4,7 +4,7 @@
 ``audio_processing.process_audio_file`` returns hands back what the fused gfx950 kernel already
 computed (per-frame E / M / ZCR and the 15-d statistics): no second pass.  Plain frame arrays
 (callers that build frames themselves) are reduced on the HIP device.  ``normalize_features``
-runs the z-score kernels (csrc/knn.hip: dsp_zscore_fit / dsp_zscore_apply).
+runs the z-score kernels (csrc/zscore.hip: dsp_zscore_fit / dsp_zscore_apply).
 """
 import numpy as np
 

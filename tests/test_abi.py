@@ -135,3 +135,26 @@ def test_no_cpu_fallback():
         knn_classify([[0.0]], [0], [[0.0]], 1)
     with pytest.raises(_hip.HipError):
         zscore_fit([[0.0]])
+
+
+def test_knndiag_layout_equals_product(monkeypatch):
+    """With no DSP_KNN_* override set, the diagnostic library (host code built with
+    -DDSP_KNN_DIAG, the product's own device objects) lays the KNN workspace out exactly as the
+    product does: seeded and unseeded matrix-core shapes, the KC = 36 pilot stride, both VALU
+    screens."""
+    from src import _hip
+    for name in ("DSP_KNN_NSPLIT", "DSP_KNN_TARGET_WGS", "DSP_KNN_SAMPLE", "DSP_KNN_SEED", "DSP_KNN_SEED_SCALE"):
+        monkeypatch.delenv(name, raising=False)
+    libs = []
+    for path in (_hip.LIB_PATH, os.path.join(os.path.dirname(_hip.LIB_PATH), "libdsp_audiorec_knndiag.so")):
+        L = ctypes.CDLL(path)
+        for fn in (L.dsp_knn_workspace_bytes, L.dsp_knn_workspace_fallbacks_offset):
+            fn.restype = ctypes.c_size_t
+            fn.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int]
+        libs.append(L)
+    for shape in [(100000, 12500, 15, 5), (100000, 100000, 15, 5), (32768, 333, 31, 25), (3000, 500, 20, 12),
+                  (2000, 300, 198, 3), (8000, 1500, 16, 5)]:
+        total = [L.dsp_knn_workspace_bytes(*shape) for L in libs]
+        fb = [L.dsp_knn_workspace_fallbacks_offset(*shape) for L in libs]
+        assert total[0] == total[1] > 0, (shape, total)
+        assert fb[0] == fb[1] > 0, (shape, fb)

@@ -98,7 +98,7 @@ def _clustered(rng, n, D, classes=10):
                                       (4000, 600, 32, 21), (3000, 500, 16, 1)])
 def test_knn_valu_direct_screen(Nr, Nq, D, k):
     """D = 16 and D = 32 leave no spare column for the expanded form, so they run the direct-form
-    VALU screen (knn_screen<DP, KC, QP>, knn.hip); k = 14 / 21 instantiate KC = 24.  Indices, fp64
+    VALU screen (knn_screen<DP, KC, QP>, knn_screen.hip); k = 14 / 21 instantiate KC = 24.  Indices, fp64
     distances and votes bit-exact against the oracle (sklearn semantics, src/models.py:33-35),
     plus the self-query exclusion (kneighbors(X=None))."""
     from src.pipeline import knn_classify
@@ -197,6 +197,35 @@ def test_knn_seeded_screen_vs_oracle(k):
     i0, d0, p0 = oracle.knn(X, y, X[lo:lo + 2000], k, n_classes=10, self_offset=lo, nthreads=16)
     assert np.array_equal(i1.cpu().numpy(), i0) and np.array_equal(d1.cpu().numpy(), d0)
     assert np.array_equal(p1.cpu().numpy(), p0)
+
+
+@pytest.mark.parametrize("D,k", [(20, 5), (20, 12), (15, 14), (31, 25)])
+def test_knn_seeded_screen_wide_rows_and_long_lists(D, k):
+    """The seeded path beyond DP = 16 / KC <= 8, at the smallest seeded set (32 768 rows, every 4th
+    a sample row) and 333 queries (no multiple of 16 or of a query block):
+      (20, 5)   knn_pilot_mfma<32>, KC 6
+      (20, 12)  KC 16: two query tiles per wave, knn_merge1<16, 16>
+      (15, 14)  KC 24: one query tile per wave in the screen against two in the pilot, so their
+                query blocks differ
+      (31, 25)  KC 36 > PIL_CLS: the pilot's workspace stride is PIL_CLS, not KC
+    once with foreign queries and once as a self-query block at row 30 001 (some queries are sample
+    rows, some are not).  Indices, fp64 distances and votes bit-exact against the oracle, and at
+    most a tenth of the queries on the fallback: a screen that certified nothing cannot pass by
+    way of the exhaustive scan.  The single-file build before the split listed 0 queries in each
+    of the eight runs on these inputs, as this one does."""
+    from src.pipeline import knn_classify
+    Nr, Nq, lo = 32768, 333, 30001
+    rng = np.random.default_rng(100 * D + k)
+    X, y = _clustered(rng, Nr, D)
+    Q, _ = _clustered(rng, Nq, D)
+    for queries, self_offset in ((Q, -1), (X[lo:lo + Nq], lo)):
+        st = {}
+        i1, d1, p1 = knn_classify(X, y, queries, k, self_offset=self_offset, stats=st)
+        i0, d0, p0 = oracle.knn(X, y, queries, k, n_classes=10, self_offset=self_offset, nthreads=16)
+        print("seeded D=%d k=%d self_offset=%d: %d of %d queries fell back" % (D, k, self_offset, st["fallbacks"], Nq))
+        assert np.array_equal(i1.cpu().numpy(), i0) and np.array_equal(d1.cpu().numpy(), d0)
+        assert np.array_equal(p1.cpu().numpy(), p0)
+        assert st["fallbacks"] <= Nq // 10, st
 
 
 @pytest.mark.parametrize("k", [5, 12, 25])
