@@ -26,6 +26,10 @@ walks the fitted tree on the device (csrc/tree.hip, dsp_tree_predict): compariso
 ``predict`` and ``apply`` are scikit-learn's with no tolerance.  Models outside the kernels' plans
 (sparse input, more than 64 classes, multi-output trees) predict through scikit-learn as before.
 
+``SequenceClassifier`` / ``create_classifier('dtw_knn')`` (an extension: the reference has no
+sequence classifier) is k-NN under dynamic time warping on the per-frame sequences (csrc/dtw.hip,
+dsp_dtw_knn): an exact fp64 distance, the KNN's voting and tie rules.
+
 ``MLPTrainer`` (models.py:109-221) trains the reference's MLP with the fused on-device trainer
 (csrc/mlp.hip: dsp_mlp_train / dsp_mlp_predict) -- the whole serial SGD loop of
 models.py:146-194 in one persistent workgroup, many epochs per launch -- or, outside that kernel's
@@ -221,6 +225,116 @@ class TraditionalClassifier:
             'predictions': y_pred,
             'classification_report': classification_report(y_test, y_pred, output_dict=True, zero_division=0),
             'confusion_matrix': confusion_matrix(y_test, y_pred),
+        }
+
+
+# ==================== DTW nearest neighbours on the frame sequences ====================
+
+def _as_padded(X, lengths):
+    """(padded float64 [N, T, F], lengths int32 [N]) from a list of [n_i, F] arrays, or from a
+    padded [N, T, F] array with its lengths.  Non-finite valid frames raise ValueError."""
+    if isinstance(X, (list, tuple)):
+        if lengths is not None:
+            raise ValueError("a list of sequences carries its own lengths")
+        seqs = [np.asarray(x, dtype=np.float64) for x in X]
+        seqs = [x.reshape(-1, 1) if x.ndim == 1 else x for x in seqs]
+        if not seqs or any(x.ndim != 2 or x.shape[1] != seqs[0].shape[1] for x in seqs):
+            raise ValueError("X must be a non-empty list of [n_i, F] arrays with one F")
+        n = np.array([len(x) for x in seqs], dtype=np.int32)
+        if n.min() < 1:
+            raise ValueError("empty sequence at index %d" % int(np.argmin(n)))
+        out = np.zeros((len(seqs), int(n.max()), seqs[0].shape[1]))
+        for i, x in enumerate(seqs):
+            out[i, :len(x)] = x
+    else:
+        out = np.array(X.cpu().numpy() if hasattr(X, 'cpu') else X, dtype=np.float64)
+        if out.ndim != 3:
+            raise ValueError("X must be a list of [n_i, F] arrays or a padded [N, T, F] array")
+        if lengths is None:
+            raise ValueError("a padded [N, T, F] array needs lengths: trailing zero rows could be real frames")
+        n = np.asarray(lengths.cpu().numpy() if hasattr(lengths, 'cpu') else lengths).astype(np.int32).reshape(-1)
+        if len(n) != len(out) or (len(n) and (n.min() < 1 or n.max() > out.shape[1])):
+            raise ValueError("lengths must be one per sequence, in [1, %d]" % out.shape[1])
+    valid = np.arange(out.shape[1])[None, :] < n[:, None]
+    if not np.isfinite(out[valid]).all():
+        raise ValueError("Input sequences contain NaN or infinity")
+    out[~valid] = 0.0  # the padding is never read as a frame; keep it finite
+    return out, n
+
+
+class SequenceClassifier:
+    """k nearest neighbours under dynamic time warping on the per-frame sequences -- the textbook
+    classifier for the (E, M, ZCR) frame features (an extension: the reference only flattens the
+    zero-padded sequences, compare_feature_methods.py:106-115).  csrc/dtw.hip (dsp_dtw_knn,
+    DESIGN.md §4.8): the exact fp64 DTW of include/dsp_audiorec.h, KNeighborsClassifier's voting and
+    tie rules as in ``TraditionalClassifier('knn')``.
+
+    X is a list of [n_i, F] arrays, or a padded [N, T, F] array together with ``lengths``.
+    window     None: unconstrained; else the Sakoe-Chiba band's half width in frames.
+    normalize  each feature channel's mean and population standard deviation over all valid frames
+               of the training sequences (numpy, std == 0 -> 1, as normalize_features), applied to
+               training and query sequences -- raw energies would drown the ZCR in the local cost.
+    No CPU path: ``predict`` raises HipError without a HIP device (``fit`` and constructing need none).
+    """
+
+    def __init__(self, n_neighbors=3, window=None, normalize=True):
+        self.n_neighbors, self.window, self.normalize = int(n_neighbors), window, bool(normalize)
+        self._index = None
+
+    def _scale(self, X, n):
+        if not self.normalize:
+            return X
+        valid = np.arange(X.shape[1])[None, :] < n[:, None]
+        out = (X - self.mean_) / self.std_
+        out[~valid] = 0.0
+        return out
+
+    def fit(self, X, y, lengths=None):
+        X, n = _as_padded(X, lengths)
+        y = np.asarray(y)
+        if len(y) != len(X):
+            raise ValueError("%d labels for %d sequences" % (len(y), len(X)))
+        if len(X) < self.n_neighbors:
+            raise ValueError("Expected n_neighbors <= n_samples_fit, but n_neighbors = %d, n_samples_fit = %d"
+                             % (self.n_neighbors, len(X)))
+        if self.normalize:
+            frames = X[np.arange(X.shape[1])[None, :] < n[:, None]]  # all valid frames, [sum n_i, F]
+            self.mean_ = np.mean(frames, axis=0)
+            std = np.std(frames, axis=0)
+            self.std_ = np.where(std == 0, 1.0, std)
+        # classes_ sorted as in scikit-learn: the vote's smallest-index tie break is the smallest label
+        self.classes_, codes = np.unique(y, return_inverse=True)
+        self._fit_X, self._fit_n, self._codes = self._scale(X, n), n, codes.astype(np.int32)
+        self._index = None  # uploaded at the first query
+        return self
+
+    def _query(self, X, lengths):
+        from .pipeline import DtwIndex
+        Xq, nq = _as_padded(X, lengths)
+        if Xq.shape[2] != self._fit_X.shape[2]:
+            raise ValueError("X has %d feature channels, the fitted sequences %d" % (Xq.shape[2], self._fit_X.shape[2]))
+        if self._index is None:
+            self._index = DtwIndex(self._fit_X, self._fit_n, self._codes, self.n_neighbors,
+                                   n_classes=len(self.classes_), window=self.window, check_finite=False)
+        return self._index.query(self._scale(Xq, nq), nq, check_finite=False)
+
+    def kneighbors(self, X, lengths=None):
+        """(distances float64, indices int64) [n, k], ascending DTW distance."""
+        idx, dist, _ = self._query(X, lengths)
+        return dist.cpu().numpy(), idx.cpu().numpy().astype(np.int64)
+
+    def predict(self, X, lengths=None):
+        _, _, pred = self._query(X, lengths)
+        return self.classes_[pred.cpu().numpy()]
+
+    def evaluate(self, X, y, lengths=None):
+        from sklearn.metrics import accuracy_score, classification_report, confusion_matrix
+        y_pred = self.predict(X, lengths)
+        return {
+            'accuracy': accuracy_score(y, y_pred),
+            'predictions': y_pred,
+            'classification_report': classification_report(y, y_pred, output_dict=True, zero_division=0),
+            'confusion_matrix': confusion_matrix(y, y_pred),
         }
 
 
@@ -490,10 +604,13 @@ def fit_mlp_models(X_train, y_train, input_size, hidden_layers, num_classes, lea
 
 
 def create_classifier(classifier_type, **kwargs):
-    """models.py:226-246.  'mlp' takes MLPTrainer's arguments.  A bare ``create_classifier('mlp')``
+    """models.py:226-246.  'mlp' takes MLPTrainer's arguments; 'dtw_knn' (an extension) is the
+    SequenceClassifier.  A bare ``create_classifier('mlp')``
     raises NotImplementedError naming them (the reference fails there with a TypeError)."""
     if classifier_type in ['knn', 'naive_bayes', 'decision_tree', 'svm']:
         return TraditionalClassifier(classifier_type, **kwargs)
+    if classifier_type == 'dtw_knn':
+        return SequenceClassifier(**kwargs)
     if classifier_type == 'mlp':
         if not kwargs:
             raise NotImplementedError("create_classifier('mlp') needs input_size, hidden_layers and num_classes "

@@ -249,6 +249,91 @@ def knn_classify(ref, ref_labels, query, k, self_offset=-1, n_classes=None, with
     return KnnIndex(ref, ref_labels, k, n_classes, with_pred).query(query, self_offset, stats)
 
 
+def _dtw_operand(seqs, lengths, device, check_finite):
+    """Padded sequences [N, T, F] and their lengths on the device as float64 / int32 (the
+    extraction's float32 ``seq`` converts exactly).  Non-finite samples raise ValueError, as
+    scikit-learn's estimators do (one host sync for a device tensor; check_finite=False skips it)."""
+    import torch
+    x = _as_device(seqs, torch.float64, device)
+    if x.dim() != 3:
+        raise ValueError("sequences must be padded to [N, T, F], got shape %s" % (tuple(x.shape),))
+    n = _as_device(lengths, torch.int32, device).reshape(-1)
+    if n.numel() != x.shape[0]:
+        raise ValueError("%d lengths for %d sequences" % (n.numel(), x.shape[0]))
+    if check_finite and x.numel() and not bool(torch.isfinite(x).all().item()):
+        raise ValueError("Input sequences contain NaN or infinity")
+    return x, n
+
+
+def _dtw_window(window):
+    return -1 if window is None or int(window) < 0 else int(window)
+
+
+def dtw_pairwise(a, len_a, b, len_b, window=None, check_finite=True):
+    """Dynamic time warping distances (include/dsp_audiorec.h: dsp_dtw_pairwise) between the padded
+    sequences a [Nq, Tq, F] and b [Nr, Tr, F] with their lengths -> dist float64 [Nq, Nr] on the
+    device.  ``window``: None / negative = unconstrained, else the Sakoe-Chiba band's half width."""
+    import torch
+    d = _hip.require_device()
+    a, len_a = _dtw_operand(a, len_a, d, check_finite)
+    b, len_b = _dtw_operand(b, len_b, d, check_finite)
+    (Nq, Tq, F), (Nr, Tr, Fb) = a.shape, b.shape
+    if F != Fb:
+        raise ValueError("sequences of %d and %d feature channels" % (F, Fb))
+    dist = torch.empty((Nq, Nr), dtype=torch.float64, device=d)
+    if Nq == 0 or Nr == 0:
+        return dist
+    nbytes = _hip.lib().dsp_dtw_workspace_bytes(Nr, Nq, Tr, Tq, F, 1)
+    if nbytes == 0:
+        raise ValueError("unsupported DTW shape (1 <= F <= 8, 1 <= T <= 1024)")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=d)
+    rc = _hip.lib().dsp_dtw_pairwise(_hip.ptr(a), _hip.ptr(len_a), Nq, Tq, _hip.ptr(b), _hip.ptr(len_b), Nr, Tr, F,
+                                     _dtw_window(window), _hip.ptr(dist), _hip.ptr(ws), nbytes, _hip.stream_handle(d))
+    _hip.check(rc, "dsp_dtw_pairwise")
+    return dist
+
+
+class DtwIndex:
+    """A reference set of padded sequences uploaded once for ``dsp_dtw_knn`` (csrc/dtw.hip), the
+    counterpart of ``KnnIndex`` under the DTW distance.  ``query`` is predict / kneighbors.  One
+    query at a time per index; the workspace grows to the largest query batch seen."""
+
+    def __init__(self, ref, len_ref, ref_labels, k, n_classes=None, window=None, check_finite=True):
+        self.device = _hip.require_device()
+        import torch
+        self.ref, self.len_ref = _dtw_operand(ref, len_ref, self.device, check_finite)
+        self.Nr, self.Tr, self.F = self.ref.shape
+        self.k = int(k)
+        self.labels = _as_device(ref_labels, torch.int32, self.device) if ref_labels is not None else None
+        self.n_classes = int(n_classes or 0)
+        self.window = _dtw_window(window)
+        self._ws = None
+
+    def query(self, seqs, lengths, self_offset=-1, check_finite=True):
+        """(idx int32 [Nq,k], dist float64 [Nq,k], pred int32 [Nq] or None) of the padded query
+        sequences [Nq, Tq, F]."""
+        import torch
+        d, k = self.device, self.k
+        q, len_q = _dtw_operand(seqs, lengths, d, check_finite)
+        Nq, Tq, F = q.shape
+        if F != self.F:
+            raise ValueError("queries of %d feature channels against references of %d" % (F, self.F))
+        nbytes = _hip.lib().dsp_dtw_workspace_bytes(self.Nr, Nq, self.Tr, Tq, F, k)
+        if nbytes == 0 and Nq > 0:
+            raise ValueError("unsupported DTW shape (1 <= F <= 8, 1 <= T <= 1024, 1 <= k <= 32)")
+        if self._ws is None or self._ws.numel() < nbytes:
+            self._ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=d)
+        idx = torch.empty((Nq, k), dtype=torch.int32, device=d)
+        dist = torch.empty((Nq, k), dtype=torch.float64, device=d)
+        pred = torch.empty(Nq, dtype=torch.int32, device=d) if self.labels is not None else None
+        rc = _hip.lib().dsp_dtw_knn(_hip.ptr(self.ref), _hip.ptr(self.len_ref), _hip.ptr(self.labels), self.Nr,
+                                    self.Tr, _hip.ptr(q), _hip.ptr(len_q), Nq, Tq, F, self.window, k,
+                                    int(self_offset), self.n_classes, _hip.ptr(idx), _hip.ptr(dist), _hip.ptr(pred),
+                                    _hip.ptr(self._ws), self._ws.numel(), _hip.stream_handle(d))
+        _hip.check(rc, "dsp_dtw_knn")
+        return idx, dist, pred
+
+
 class SvcIndex:
     """A fitted ``sklearn.svm.SVC(kernel='rbf')`` uploaded once for ``dsp_svc_predict``
     (csrc/svm.hip): libsvm's own arrays -- support_vectors_, _n_support, _dual_coef_, _intercept_,

@@ -36,7 +36,7 @@ extern "C" {
                               5: queue_ws is 4 KiB (each counter on its own 256-B line);
                               6: the extraction entry points take out_stride (packed result rows);
                                  dsp_knn_classify takes flags (DSP_KNN_REF_READY).
-                              Still 6 with the dsp_mlp_*, dsp_svc_*, dsp_gnb_* and dsp_tree_* entry points: new symbols only, no
+                              Still 6 with the dsp_mlp_*, dsp_svc_*, dsp_gnb_*, dsp_tree_* and dsp_dtw_* entry points: new symbols only, no
                               existing signature or meaning changed, so callers built against 6 keep
                               working (a binding that needs them checks for the symbols) */
 
@@ -389,6 +389,53 @@ int dsp_tree_predict(const int32_t *children_left, const int32_t *children_right
                      const double *threshold, const int32_t *leaf_class, int64_t n_nodes, int max_depth,
                      int D, const double *X, int64_t Nq, int32_t *pred, int32_t *leaf, void *workspace,
                      size_t workspace_bytes, void *stream);
+
+/*
+ * Dynamic time warping (DTW) and its k nearest neighbours -- the textbook classifier for the
+ * per-frame (E, M, ZCR) sequences that dsp_extract_features writes to `seq` (the reference only
+ * zero-pads and flattens them, compare_feature_methods.py:106-115).  csrc/dtw.hip, DESIGN.md §4.8.
+ *
+ * Sequences are float64, padded row-major: a [Nq, Tq, F] with len_a int32 [Nq], b [Nr, Tr, F] with
+ * len_b int32 [Nr]; 1 <= F <= 8, 1 <= Tq, Tr <= 1024.  For a pair with lengths n, m:
+ *   c(i,j) = sum_f (a[i,f] - b[j,f])^2    f ascending, fp64, each product and each sum rounded (no FMA)
+ *   D(0,0) = c(0,0)
+ *   D(i,j) = c(i,j) + min(D(i-1,j), D(i,j-1), D(i-1,j-1))   neighbours outside the grid or the band are +inf
+ *   dtw    = sqrt(D(n-1, m-1))
+ * window < 0: unconstrained.  window >= 0: a Sakoe-Chiba band, cell (i,j) admissible iff
+ * |i - j| <= max(window, |n - m|), so the end cell is always reachable.
+ * Only fp64 subtract, multiply, add, min and sqrt occur, all correctly rounded, and min is
+ * order-independent on non-negative finite values: the result is defined bit for bit, and a pair's
+ * bits do not depend on Nq, Nr, the pair's position, the tile it lands in or the launch shape.
+ * A sequence whose length is < 1 or greater than its padded width has distance +inf to everything;
+ * no row is read outside its padded width.  Non-finite sample values: the result is unspecified (the
+ * Python surface rejects them), but the kernel terminates and stays in bounds.
+ *
+ * dsp_dtw_pairwise: dist float64 [Nq, Nr].
+ * dsp_dtw_knn: the k nearest reference sequences of each query under dtw, by dsp_knn_classify's
+ *   rules: 1 <= k <= 32, ascending distance (the dtw value dsp_dtw_pairwise returns), exact-distance
+ *   ties ordered by the smaller reference index, idx = -1 and dist = +inf where fewer than k
+ *   references at a finite distance exist, self_offset >= 0 excludes reference row self_offset + q,
+ *   a uniform vote in which the smallest label wins ties (pred = -1 without any neighbour); a NULL
+ *   pred or NULL ref_labels skips the vote.  ref_labels int32 [Nr] >= 0; n_classes is informational.
+ *   idx int32 [Nq, k], dist float64 [Nq, k], pred int32 [Nq].
+ * workspace  device scratch of dsp_dtw_workspace_bytes(Nr, Nq, Tr, Tq, F, k) bytes (0: sizes outside
+ *   the plan -- the limits above, 1 <= k <= 32, Nr < 2^31).  It stays bounded whatever Nq is: both
+ *   entry points work through the queries in chunks of at most 1024 queries and at most 64 MiB of
+ *   distance rows (one row when a single row is larger), and the workspace holds, for one chunk, the
+ *   strips' edge columns of at most 4096 resident waves (at most 256 MiB, and only when Tq > 32), a
+ *   copy of the chunk's queries behind 32 frames of zeros (at most 1024 x 1056 x F doubles, 66 MiB)
+ *   and, for dsp_dtw_knn, the chunk's distance rows -- never the full [Nq, Nr] matrix.
+ *   dsp_dtw_pairwise writes its rows straight to dist and accepts any workspace that holds the first
+ *   two parts; the size for k = 1 always does.
+ */
+size_t dsp_dtw_workspace_bytes(int64_t Nr, int64_t Nq, int Tr, int Tq, int F, int k);
+int dsp_dtw_pairwise(const double *a, const int32_t *len_a, int64_t Nq, int Tq, const double *b,
+                     const int32_t *len_b, int64_t Nr, int Tr, int F, int window, double *dist,
+                     void *workspace, size_t workspace_bytes, void *stream);
+int dsp_dtw_knn(const double *ref, const int32_t *len_ref, const int32_t *ref_labels, int64_t Nr, int Tr,
+                const double *query, const int32_t *len_query, int64_t Nq, int Tq, int F, int window,
+                int k, int64_t self_offset, int n_classes, int32_t *idx, double *dist, int32_t *pred,
+                void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * Batch WAV reader -- host only (no GPU, no stream): the file side of load_wav
