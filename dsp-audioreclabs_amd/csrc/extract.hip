@@ -544,7 +544,9 @@ __device__ __forceinline__ void r1_redo_s2(const short8 *q, int w, unsigned long
     wS2[w] = s2;
 }
 // lane l: sample l & 31 of the first word (l < 32) or of the last (l >= 32, clips of two words or
-// more); issued at R1's start, consumed (r1_edges) after the interior words
+// more); issued and consumed (r1_edges) after the last wave's interior words (the listing has the
+// 16-bit load there).  Issued at R1's start instead, one VGPR held across the interior words: 100k
+// clips 2.315 against 2.308 ms, no gain (profiles/w7_ab.txt)
 __device__ __forceinline__ int r1_edge_issue(const ExtractParams &p, const ClipRef &cur, int lane)
 {
     const int w = lane < 32 ? 0 : cur.nword - 1, u = 32 * w + (lane & 31);
@@ -830,13 +832,15 @@ __device__ __forceinline__ void vad_frames_fast(const Ctx &c, const ClipRef &cur
 // VGPR spills; 9 (a whole 1102-sample frame) 2.71 ms, 7 2.65 ms, 6 / 8 2.61-2.64 / 2.66-2.68 ms at
 // 100k clips (profiles/r05s_ab_prefetch_kv.txt, r05kv_ab_r4_batch.txt)
 static constexpr int R4_KV = 7;
-template <bool ZSEG>  // ZCR from R2's segment prefixes (clip_fast) or by the row's lanes (clip_body)
+// frames of a crop of m = en - st samples (frame_signal, :299-333)
+__device__ __forceinline__ int crop_frame_count(int m, int L, int S) { return (m <= L) ? 1 : (m - L + S - 1) / S + 1; }
+template <bool ZSEG>  // ZCR left to crop_zcr (clip_fast: fE / fM only) or by the row's lanes (clip_body)
 __device__ __forceinline__ int r4_frames(const ExtractParams &p, const Ctx &c, const ClipRef &cur, int L, int S,
                                          int st, int en, const ClipStats &cs, int j0, int j1, int wrank, int lane)
 {
     const int n = cur.n, lead = cur.lead;
     const int m = en - st;  // > 0 always (start < end)
-    const int F = (m <= L) ? 1 : (m - L + S - 1) / S + 1;
+    const int F = crop_frame_count(m, L, S);
     const float sE = cs.invMf * cs.invMf, sM = cs.invMf;
     const int wrow = EXTRACT_WROW(L);
     const CanonX cx = canon_x(cs.mq, cs.t0);
@@ -910,13 +914,7 @@ __device__ __forceinline__ int r4_frames(const ExtractParams &p, const Ctx &c, c
         // [j0, j1]) and j < lim; transitions into the window's zero ends / padding count too
         const int ia = fs + j0, ib = min(fs + j1, en - 1);  // sample coords
         int z = 0;
-        if constexpr (ZSEG) {  // one lane per frame
-            if (rl == 0 && ia <= ib) {
-                z = zseg_count(c.posw, c.zw, c.ztot, ia + lead, ib + lead);
-                if (j0 > 0) z += pos_bit(c.posw, ia + lead);
-                if (ib < fs + L - 1) z += pos_bit(c.posw, ib + lead);
-            }
-        } else {
+        if constexpr (!ZSEG) {
             z = dpp_row_reduce(ia < ib ? chg_count(c.posw, ia + lead, ib + lead, rl, 16) : 0, OpAdd());
             if (ia <= ib) {
                 if (j0 > 0) z += pos_bit(c.posw, ia + lead);
@@ -926,10 +924,28 @@ __device__ __forceinline__ int r4_frames(const ExtractParams &p, const Ctx &c, c
         if (act && rl == 0) {
             c.fE[g] = E1;
             c.fM[g] = M1;
-            c.fZ[g] = z;
+            if constexpr (!ZSEG) c.fZ[g] = z;
         }
     }
     return F;
+}
+// FAST R4: the crop frames' ZCR (r4_frames' formula) by ONE wave, a lane per frame, from R2's
+// segment prefixes -> c.fZ.  On the row waves this integer work ran with 4 lanes of 64 active (lane
+// 0 of each 16-lane row), once per group of four frames and after the row's loads and sums.
+__device__ __forceinline__ void crop_zcr(const Ctx &c, int lead, int L, int S, int st, int en, int F, int j0, int j1,
+                                         int lane)
+{
+    for (int g = lane; !(DSP_ABL & 1) && g < F; g += 64) {
+        const int fs = st + g * S;
+        const int ia = fs + j0, ib = min(fs + j1, en - 1);  // sample coords (see r4_frames)
+        int z = 0;
+        if (ia <= ib) {
+            z = zseg_count(c.posw, c.zw, c.ztot, ia + lead, ib + lead);
+            if (j0 > 0) z += pos_bit(c.posw, ia + lead);
+            if (ib < fs + L - 1) z += pos_bit(c.posw, ib + lead);
+        }
+        c.fZ[g] = z;
+    }
 }
 
 // R5 for F <= 32 (the typical crop): four jobs on waves 0..3 instead of r5_fast's six -- two
@@ -1241,7 +1257,11 @@ __device__ __forceinline__ void stage_outputs(const Ctx &c, int i, int st, int e
 // arithmetic), and the DMA's round trip sat on the critical path.  Rows of the next clip's words
 // loaded during R5 (the rest at its start): 1 row 3.52 ms, 2 rows 3.70 ms against 2.85 ms without at
 // 100k clips (spills; profiles/r05j_ab_prefetch_rows.txt), and with 0 spills 2.65-2.68 against
-// 2.65 ms (r05s_ab_prefetch_kv.txt): not kept.
+// 2.65 ms (r05s_ab_prefetch_kv.txt): not kept.  The next clip warmed into L2 without registers -- the
+// last wave, idle in R4 at F <= 28, loading one dword of each of its 128-B lines and discarding it:
+// 2.587 ms issued at R4's start, 2.497 at R5's, against 2.310 (any cache policy; profiles/w7_ab.txt).
+// FETCH_SIZE rose by 49% / 21%: the touched lines were evicted again before their use; and a touch
+// presumably moves its whole line into the CU's vector cache, the clip crossing that path twice.
 
 // One clip, FAST layout, not the exact redo; its RREG words are already in flight into regs (word
 // r * NT + tid in regs[4r .. 4r+3]).  Endpoint energies from exact moments, decisions certified;
@@ -1367,6 +1387,9 @@ __device__ __forceinline__ bool clip_fast(const ExtractParams &p, const Ctx &c, 
 
     // ---- R4: windowed frames over the crop [st, en) (r4_frames) --------------------------------
     MARK(R4);
+    // the ZCR of every crop frame on the last wave, which holds no rows up to F = 4 (NWAVE - 1) = 28
+    // frames (the typical crop) and otherwise counts before them; the row waves write fE / fM only
+    if (wid == NWAVE - 1) crop_zcr(c, lead, L, S, st, en, crop_frame_count(en - st, L, S), sh->j0, sh->j1, lane);
     const int F = r4_frames<true>(p, c, cur, L, S, st, en, cs, sh->j0, sh->j1, wid, lane);
     STAMP(i, 12);
     __syncthreads();
