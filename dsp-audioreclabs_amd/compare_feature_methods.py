@@ -39,14 +39,16 @@ def load_both_methods(data_dir=None, frame_length=None, frame_shift=None, window
     return X_stat, X_seq, y, lengths
 
 
-def compare(data_dir=None, classifiers=None, test_size=0.2, random_state=42, dtw=False):
+def compare(data_dir=None, classifiers=None, test_size=0.2, random_state=42, dtw=False, dtw_template=False):
     """:124-214: each classifier on both feature sets, the reference's split and normalisation
     -> {classifier: {'statistical': acc, 'sequence': acc, 'diff': sequence - statistical}}.
     KNN on the flattened sequences (2 x max_frames columns) runs on the device like the 15-d
     case (dsp_knn_classify's chunked high-dimensional screen + fp64 re-rank).
     dtw=True (an extension) adds the row 'KNN-DTW': 'statistical' is the KNN's statistical accuracy,
     'sequence' the accuracy of k-NN under dynamic time warping (src.models.SequenceClassifier,
-    n_neighbors=3) on the UNPADDED (E, ZCR) sequences of the same split."""
+    n_neighbors=3) on the UNPADDED (E, ZCR) sequences of the same split.
+    dtw_template=True (an extension) adds the row 'DTW-template' beside it: the same, for the nearest
+    of one DBA template per class (src.models.TemplateClassifier, its defaults)."""
     from sklearn.model_selection import train_test_split
     X_stat, X_seq, y, lengths = load_both_methods(data_dir)
     X_flat = X_seq.reshape(len(X_seq), -1)
@@ -66,18 +68,21 @@ def compare(data_dir=None, classifiers=None, test_size=0.2, random_state=42, dtw
             acc[method] = float(clf.evaluate(te, y_te)['accuracy'])
         results[name] = {'statistical': acc['statistical'], 'sequence': acc['sequence'],
                          'diff': acc['sequence'] - acc['statistical']}
-    if dtw:
+    if dtw or dtw_template:
         tr, te = train_test_split(np.arange(len(y)), test_size=test_size, random_state=random_state, stratify=y)
         lengths = np.asarray(lengths)
-        clf = create_classifier('dtw_knn', n_neighbors=3).fit(X_seq[tr], y[tr], lengths=lengths[tr])
-        seq_acc = float(clf.evaluate(X_seq[te], y[te], lengths=lengths[te])['accuracy'])
         if 'KNN' in results:
             stat_acc = results['KNN']['statistical']
         else:
             kind, params = CLASSIFIERS['KNN']
             knn = create_classifier(kind, **params).fit(Xs_tr, y_tr)
             stat_acc = float(knn.evaluate(Xs_te, y_te)['accuracy'])
-        results['KNN-DTW'] = {'statistical': stat_acc, 'sequence': seq_acc, 'diff': seq_acc - stat_acc}
+        rows = ([('KNN-DTW', 'dtw_knn', {'n_neighbors': 3})] if dtw else []) + \
+               ([('DTW-template', 'dtw_template', {})] if dtw_template else [])
+        for name, kind, params in rows:
+            clf = create_classifier(kind, **params).fit(X_seq[tr], y[tr], lengths=lengths[tr])
+            seq_acc = float(clf.evaluate(X_seq[te], y[te], lengths=lengths[te])['accuracy'])
+            results[name] = {'statistical': stat_acc, 'sequence': seq_acc, 'diff': seq_acc - stat_acc}
     return results
 
 

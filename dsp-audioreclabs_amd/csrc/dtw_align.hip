@@ -1,0 +1,495 @@
+// dtw_align.hip -- the warping path of dynamic time warping and one DTW barycentre averaging (DBA)
+// update on it, on gfx950 (include/dsp_audiorec.h: dsp_dtw_align, dsp_dtw_dba_update).
+// c, D, the band and invalid lengths are dtw.hip's, unchanged.
+//
+// Path.  For a pair with lengths n (side a, index i) and m (side b, index j), walk back from
+// (n-1, m-1) to (0, 0): the predecessor of (i, j) is the FIRST of (i-1, j-1), (i-1, j), (i, j-1)
+// whose D equals the minimum of the three, neighbours outside the grid or the band counting as
+// +inf.  D is defined bit for bit, so the path is.  The tie rule is stated in a / b indices and is
+// not symmetric: this kernel walks the grid transposed (a along the register strip) and names its
+// neighbours accordingly -- "left" in the strip is (i-1, j), the row above is (i, j-1).
+// Ranges.  From a's side, two int32 rows per pair: frame i of a is matched to frames lo[i] .. hi[i]
+// of b; lo[0] = 0, hi[n-1] = m-1, hi[i] <= lo[i+1] <= hi[i] + 1, and the path's cells are exactly
+// {(i, j): lo[i] <= j <= hi[i]}.  Entries i >= n are -1; a pair with an invalid length on either
+// side (or a members entry outside [0, Nb)) has dist = +inf and every entry -1.
+// Pairs.  A CSR list over a: the sequences aligned to a[c] are b[members[p]] for p in
+// [group_start[c], group_start[c+1]); outputs are indexed by p.
+// One DBA update, template c of length L, valid members k0 < k1 < ... in list order:
+//   S_k[i,f] = s_k[lo,f] + s_k[lo+1,f] + ... + s_k[hi,f]      left to right, each sum rounded
+//   acc[i,f] = S_k0[i,f];  acc = acc + S_k for k1, k2, ...    in list order
+//   cnt[i]   = sum_k (hi - lo + 1)                            integer
+//   new[i,f] = acc[i,f] / (double)cnt[i]                      one rounded division
+//   inertia  = D_k0(end);  inertia = inertia + D_k(end)       (dtw^2, before the sqrt) in list order
+// Rows i >= L of the output are zeros; a template whose own length is invalid or that has no valid
+// member is copied bit for bit with inertia 0.0.
+//
+// Kernels:
+//   dtw_align_dp<F>  dtw_dp<F>'s shape: one wave per tile of 64 members of ONE group, the group's a
+//              sequence wave-uniform (scalar loads from a copy behind 32 zero frames), a lane per
+//              member, 32 cells of an end-aligned strip in registers, the edge column through a
+//              per-wave [row][lane] array.  Beyond D each cell yields two bits (does D(i-1, j-1),
+//              does D(i-1, j) equal the minimum: the rule's first two candidates); the 2 x 32 bits
+//              of a strip row are one 64-bit word per lane, stored [strip][row][lane] -- one
+//              coalesced 512-byte store per row, nothing per cell.
+//              After the tile's strips each lane walks its own path back through those words (at
+//              most n + m - 1 steps; a word is re-read only when the strip or the row changes) and
+//              writes lo / hi.  The walk clamps at i = 0 and j = 0, so it ends and stays inside the
+//              pair's words whatever the codes hold.  Waves are persistent: wave w of G takes the
+//              tiles w, w + G, ... of the launch's groups, counted by walking group_start (scalar
+//              loads, at most 1024 groups per launch), so the words and the edges are per wave and
+//              bounded whatever P is.
+//   dtw_align_pad    the padded copy of a chunk of a.
+//   dba_sums   a thread per (pair, frame, channel): S_k from the pair's ranges, all pairs in parallel.
+//   dba_accumulate / dba_finish   a thread per (template, frame, channel): acc = acc + S_k over the
+//              chunk's pairs in list order, then the division.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+
+#include "dsp_audiorec.h"
+#include "dtw_internal.h"
+
+namespace dsp {
+
+static constexpr size_t DTW_ALIGN_WAVE_CAP = 1024u << 20;  // bytes of code words and edges per launch
+static constexpr size_t DTW_ALIGN_RANGE_CAP = 128u << 20;  // bytes of lo, hi and S_k per DBA pair chunk
+static constexpr int DTW_ALIGN_GCHUNK = 1024;              // groups per launch at most
+static constexpr int DBA_BATCH = 16;                       // members whose loads a DBA thread keeps in flight
+
+#pragma clang fp contract(off)
+// dtw_row (dtw.hip) with the predecessor codes: cells (r, c0 .. c0 + 31) of a strip, r the b frame,
+// c the a frame.  prev holds the row above -- D(i, j-1) -- and is replaced; diag = D(i-1, j-1),
+// left = D(i-1, j).  w0 collects "the diagonal equals the minimum", w1 "the a-step (i-1, j) does", one
+// bit per cell, cell 31 in bit 0: diagonal if w0's bit is set, else a-step if w1's is, else b-step.
+template <int F, int MODE>
+__device__ __forceinline__ void dtw_row_dir(double (&prev)[DTW_STRIP], double diag, double left, const double (&bf)[F],
+                                            const double *__restrict__ qs, int c0, int r, int w, uint32_t &w0,
+                                            uint32_t &w1)
+{
+    uint32_t md = 0, ml = 0;
+#pragma unroll
+    for (int j = 0; j < DTW_STRIP; j++) {
+        const int c = c0 + j;
+        const double *qc = qs + j * F;
+        double t = bf[0] - qc[0];
+        double cost = t * t;
+#pragma unroll
+        for (int f = 1; f < F; f++) {
+            t = bf[f] - qc[f];
+            cost = cost + t * t;
+        }
+        double best = dtw_min(dtw_min(prev[j], left), diag);
+        // m = 2 m + (x == best): each compare's bit is shifted in through the carry, two instructions
+        // per bit (a select and an or of a constant per bit are three)
+        asm("v_cmp_eq_f64 vcc, %2, %4\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc\n\t"
+            "v_cmp_eq_f64 vcc, %3, %4\n\tv_addc_co_u32 %1, vcc, %1, %1, vcc"
+            : "+v"(md), "+v"(ml)
+            : "v"(diag), "v"(left), "v"(best)
+            : "vcc");
+        if (MODE == 2 && c == 0) best = 0.0;  // D(0,0) = c(0,0)
+        double v = cost + best;
+        if (MODE != 0) {
+            const int d = r - c;
+            v = (d < 0 ? -d : d) <= w ? v : (double)INFINITY;
+        }
+        diag = prev[j];
+        prev[j] = v;
+        left = v;
+    }
+    w0 = md;
+    w1 = ml;
+}
+#pragma clang fp contract(on)
+
+// apad [nc, Ta + DTW_STRIP, F]: DTW_STRIP frames of zeros, then a's row (dtw_pad's layout)
+__global__ __launch_bounds__(256) void dtw_align_pad(const double *__restrict__ a, int64_t nc, int Ta, int F,
+                                                     double *__restrict__ apad)
+{
+    const int64_t rowp = (int64_t)(Ta + DTW_STRIP) * F, total = nc * rowp;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t q = i / rowp, e = i - q * rowp - (int64_t)DTW_STRIP * F;
+        apad[i] = e < 0 ? 0.0 : a[q * Ta * F + e];
+    }
+}
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// The groups c = 0 .. nc-1 of this launch (apad, len_a and group_start already point at the first
+// one) and of their pairs those in [p_lo, p_hi).  dist is indexed by p; d2 (D(end) before the sqrt),
+// lo and hi by p - p_lo.  Any of dist, d2 and the lo / hi pair may be NULL.
+template <int F>
+__global__ __launch_bounds__(64) void dtw_align_dp(const double *__restrict__ apad, const int32_t *__restrict__ len_a,
+                                                   const int32_t *__restrict__ group_start, int nc, int Ta,
+                                                   const double *__restrict__ b, const int32_t *__restrict__ len_b,
+                                                   int64_t Nb, int Tb, const int32_t *__restrict__ members, int p_lo,
+                                                   int p_hi, int window, double *__restrict__ dist,
+                                                   double *__restrict__ d2, int32_t *__restrict__ lo,
+                                                   int32_t *__restrict__ hi, double *__restrict__ edge_ws,
+                                                   unsigned long long *dir_ws)
+{
+    const int lane = (int)threadIdx.x;
+    const int G = (int)gridDim.x, wv = (int)blockIdx.x;
+    const int smax = (Ta + DTW_STRIP - 1) / DTW_STRIP;
+    double *__restrict__ edge = edge_ws + (size_t)wv * (size_t)Tb * 64 + lane;
+    unsigned long long *dir = dir_ws + (size_t)wv * (size_t)smax * (size_t)Tb * 64 + lane;  // [strip][row][lane]
+    int base = 0;  // tiles of the groups before c, modulo G
+    for (int cg = 0; cg < nc; cg++) {
+        const int g0 = clampi(group_start[cg], p_lo, p_hi), g1 = clampi(group_start[cg + 1], p_lo, p_hi);
+        if (g1 <= g0) continue;
+        const int nt = (int)(((int64_t)g1 - g0 + 63) / 64);
+        int t0 = wv - base;
+        if (t0 < 0) t0 += G;
+        base = (int)(((int64_t)base + nt) % G);
+        if (t0 >= nt) continue;
+        const int n = len_a[cg];
+        const bool nok = n >= 1 && n <= Ta;
+        const double *__restrict__ q = apad + ((int64_t)cg * (Ta + DTW_STRIP) + DTW_STRIP) * F;  // frame 0
+        const int S = nok ? (n + DTW_STRIP - 1) / DTW_STRIP : 0;
+        for (int t = t0; t < nt; t += G) {
+            const int64_t p = (int64_t)g0 + (int64_t)t * 64 + lane;
+            const bool inr = p < g1;
+            const int ref = inr ? members[p] : -1;
+            const bool rok = ref >= 0 && ref < Nb;
+            int m = rok ? len_b[ref] : 0;
+            if (m < 1 || m > Tb) m = 0;
+            double res = INFINITY;
+            const int mmax = wave_max_uniform(m);
+            if (nok && mmax > 0) {
+                const double *__restrict__ br = b + (int64_t)(rok ? ref : 0) * Tb * F;
+                const int dl = n > m ? n - m : m - n;
+                const int w = window < 0 ? DTW_WBIG : min(max(window, dl), DTW_WBIG);
+                const int wmax = wave_max_uniform(m > 0 ? w : 0);
+                const int wmin = -wave_max_uniform(m > 0 ? -w : -DTW_WBIG);
+                for (int s = 0; s < S; s++) {
+                    const int c0 = n - DTW_STRIP * (S - s);  // end-aligned: c0 < 0 only in strip 0
+                    const int cf = max(c0, 0);
+                    const int rlo = max(0, cf - wmax), rhi = min(mmax, c0 + DTW_STRIP + wmax);
+                    if (rlo >= rhi) continue;
+                    const bool has_left = s > 0, has_right = s < S - 1;
+                    const double *__restrict__ qs = q + c0 * F;
+                    unsigned long long *drow = dir + (size_t)s * (size_t)Tb * 64;
+                    double prev[DTW_STRIP];
+#pragma unroll
+                    for (int j = 0; j < DTW_STRIP; j++) prev[j] = INFINITY;
+                    auto left_of = [&](int r) {  // D(r, c0 - 1) from the strip before, +inf outside the band
+                        const int d = r - (c0 - 1);
+                        return (has_left && (d < 0 ? -d : d) <= w) ? edge[(size_t)r * 64] : (double)INFINITY;
+                    };
+                    double dg = rlo > 0 ? left_of(rlo - 1) : (double)INFINITY;
+                    double bf[F], left = left_of(rlo);
+#pragma unroll
+                    for (int f = 0; f < F; f++) bf[f] = br[(size_t)rlo * F + f];
+                    for (int r = rlo; r < rhi; r++) {
+                        const int rn = min(r + 1, rhi - 1);  // the next row's loads, issued before this row's cells
+                        double bfn[F];
+#pragma unroll
+                        for (int f = 0; f < F; f++) bfn[f] = br[(size_t)rn * F + f];
+                        const double leftn = left_of(rn);
+                        const bool full = r > 0 && r - cf <= wmin && c0 + DTW_STRIP - 1 - r <= wmin;
+                        uint32_t w0, w1;
+                        if (r == 0)
+                            dtw_row_dir<F, 2>(prev, dg, left, bf, qs, c0, r, w, w0, w1);
+                        else if (full)
+                            dtw_row_dir<F, 0>(prev, dg, left, bf, qs, c0, r, w, w0, w1);
+                        else
+                            dtw_row_dir<F, 1>(prev, dg, left, bf, qs, c0, r, w, w0, w1);
+                        dg = left;
+                        if (lo) drow[(size_t)r * 64] = ((unsigned long long)w1 << 32) | w0;
+                        if (has_right)
+                            edge[(size_t)r * 64] = prev[DTW_STRIP - 1];
+                        else if (r == m - 1)
+                            res = prev[DTW_STRIP - 1];
+                        left = leftn;
+#pragma unroll
+                        for (int f = 0; f < F; f++) bf[f] = bfn[f];
+                    }
+                }
+            }
+            if (!inr) continue;
+            if (dist) dist[p] = res < INFINITY ? sqrt(res) : (double)INFINITY;
+            if (d2) d2[p - p_lo] = res;
+            if (!lo) continue;
+            int32_t *__restrict__ plo = lo + (p - p_lo) * Ta, *__restrict__ phi = hi + (p - p_lo) * Ta;
+            int filled = 0;
+            if (nok && m > 0) {
+                // the lane's own walk back; cell (i, j) sits in strip S-1 - (n-1-i)/32 at bit
+                // (n-1-i)%32 of both halves of row j's word (the strip's last cell was shifted in last)
+                int i = n - 1, j = m - 1, ks = -1, kr = -1;
+                unsigned long long word = 0;
+                phi[i] = j;
+                while (i > 0 || j > 0) {
+                    const int k = n - 1 - i, s = S - 1 - (k >> 5), bit = k & 31;
+                    if (s != ks || j != kr) {
+                        word = dir[((size_t)s * Tb + j) * 64];
+                        ks = s;
+                        kr = j;
+                    }
+                    int code = ((word >> bit) & 1) ? 0 : (((word >> (32 + bit)) & 1) ? 1 : 2);
+                    if (i == 0)
+                        code = 2;
+                    else if (j == 0)
+                        code = 1;
+                    if (code == 2) {
+                        j--;
+                    } else {
+                        plo[i] = j;
+                        i--;
+                        if (code == 0) j--;
+                        phi[i] = j;
+                    }
+                }
+                plo[0] = 0;
+                filled = n;
+            }
+            for (int i = filled; i < Ta; i++) {
+                plo[i] = -1;
+                phi[i] = -1;
+            }
+        }
+    }
+}
+
+#pragma clang fp contract(off)
+// S_k of the launch's groups' pairs in [p_lo, p_hi) -- one run of pairs, the list being CSR: only
+// their ranges were written -- a thread per (pair, frame i, channel f): the member's frames lo .. hi
+// added left to right into sums [pair - p_lo][i][f].  A pair with an invalid length has lo = -1 and
+// nothing of it is read; rows behind the template's length hold -1 as well.  (A group_start that is
+// not non-decreasing breaks the "one run" and leaves rows nobody wrote: the range and the member are
+// checked against the sequence's bounds, so such a list gives wrong sums but reads nothing outside.)
+__global__ __launch_bounds__(256) void dba_sums(const double *__restrict__ seqs, int64_t N, int Ts, int F, int Tt,
+                                                const int32_t *__restrict__ group_start, int nc,
+                                                const int32_t *__restrict__ members, int p_lo, int p_hi,
+                                                const int32_t *__restrict__ lo, const int32_t *__restrict__ hi,
+                                                double *__restrict__ sums)
+{
+    const int q_lo = clampi(group_start[0], p_lo, p_hi), q_hi = clampi(group_start[nc], p_lo, p_hi);
+    const int64_t first = (int64_t)(q_lo - p_lo) * Tt * F, total = (int64_t)(q_hi - p_lo) * Tt * F;
+    for (int64_t e = first + (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+        const int f = (int)(e % F);
+        const int64_t row = e / F;  // (pair - p_lo) * Tt + i
+        const int l = lo[row];
+        if (l < 0) continue;
+        const int h = hi[row], mem = members[p_lo + row / Tt];
+        if (h < l || h >= Ts || mem < 0 || mem >= N) continue;
+        const double *__restrict__ s = seqs + (int64_t)mem * Ts * F + f;
+        double sum = s[(int64_t)l * F];
+        for (int j = l + 1; j <= h; j++) sum = sum + s[(int64_t)j * F];
+        sums[e] = sum;
+    }
+}
+
+// One thread per (template c, frame i, channel f) of the launch's groups: acc = acc + S_k over the
+// pairs of [p_lo, p_hi) in list order (lo, hi, sums, d2 indexed by p - p_lo).  acc (the output
+// templates), cnt and inertia carry the sums from one pair chunk to the next; cnt == 0: no valid
+// member seen yet.  The loads of DBA_BATCH members are issued together (none depends on another);
+// the additions stay in list order.
+__global__ __launch_bounds__(256) void dba_accumulate(int F, const int32_t *__restrict__ group_start, int nc, int Tt,
+                                                      const int32_t *__restrict__ len_t, int p_lo, int p_hi,
+                                                      const int32_t *__restrict__ lo, const int32_t *__restrict__ hi,
+                                                      const double *__restrict__ sums,
+                                                      const double *__restrict__ d2, double *__restrict__ acc,
+                                                      int32_t *__restrict__ cnt, double *__restrict__ inertia)
+{
+    const int64_t total = (int64_t)nc * Tt * F;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+        const int f = (int)(e % F), i = (int)((e / F) % Tt), c = (int)(e / ((int64_t)F * Tt));
+        const int L = len_t[c];
+        if (L < 1 || L > Tt || i >= L) continue;
+        const int g0 = clampi(group_start[c], p_lo, p_hi), g1 = clampi(group_start[c + 1], p_lo, p_hi);
+        const bool lead = i == 0 && f == 0 && inertia;
+        int count = cnt[e];
+        double a = acc[e], in = lead ? inertia[c] : 0.0;
+        for (int p0 = g0; p0 < g1; p0 += DBA_BATCH) {
+            int l[DBA_BATCH], h[DBA_BATCH];
+            double sum[DBA_BATCH], dd[DBA_BATCH];
+#pragma unroll
+            for (int u = 0; u < DBA_BATCH; u++) {
+                const bool in_group = p0 + u < g1;
+                const int64_t row = (int64_t)(p0 + u - p_lo) * Tt + i;
+                l[u] = in_group ? lo[row] : -1;
+                h[u] = in_group ? hi[row] : -1;
+                sum[u] = in_group ? sums[row * F + f] : 0.0;  // not written for an invalid pair, not used then
+                dd[u] = lead && in_group ? d2[p0 + u - p_lo] : 0.0;
+            }
+#pragma unroll
+            for (int u = 0; u < DBA_BATCH; u++) {
+                if (l[u] < 0) continue;
+                a = count == 0 ? sum[u] : a + sum[u];
+                if (lead) in = count == 0 ? dd[u] : in + dd[u];
+                count += h[u] - l[u] + 1;
+            }
+        }
+        acc[e] = a;
+        cnt[e] = count;
+        if (lead) inertia[c] = in;
+    }
+}
+
+// cnt = 0 before a group chunk's first pair chunk.  A kernel, not a memset: the call stays a chain of
+// kernel launches, which is what a captured single-stream graph of it replays in order.
+__global__ __launch_bounds__(256) void dba_begin(int32_t *__restrict__ cnt, int64_t total)
+{
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) cnt[e] = 0;
+}
+
+// acc / cnt, zeros behind the template's length; the template itself where nothing was summed
+__global__ __launch_bounds__(256) void dba_finish(const double *__restrict__ tmpl, const int32_t *__restrict__ len_t,
+                                                  int nc, int Tt, int F, const int32_t *__restrict__ cnt,
+                                                  double *__restrict__ out, double *__restrict__ inertia)
+{
+    const int64_t total = (int64_t)nc * Tt * F;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+        const int f = (int)(e % F), i = (int)((e / F) % Tt), c = (int)(e / ((int64_t)F * Tt));
+        const int L = len_t[c];
+        const bool summed = L >= 1 && L <= Tt && cnt[(int64_t)c * Tt * F] > 0;
+        out[e] = !summed ? tmpl[e] : (i < L ? out[e] / (double)cnt[e] : 0.0);
+        if (!summed && i == 0 && f == 0 && inertia) inertia[c] = 0.0;
+    }
+}
+#pragma clang fp contract(on)
+
+// ---- host side ----
+static bool align_in_plan(int64_t Na, int64_t Nb, int64_t P, int Ta, int Tb, int F)
+{
+    return Na >= 0 && Na < 0x7fffffff && Nb >= 0 && Nb <= 0x7fffffff && P >= 0 && P <= 0x7fffffff && Ta >= 1 &&
+           Ta <= DTW_TMAX && Tb >= 1 && Tb <= DTW_TMAX && F >= 1 && F <= DTW_FMAX;
+}
+static size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+// a wave's code words [strips][Tb][64] and its edge column [Tb][64]
+static size_t align_wave_bytes(int Ta, int Tb)
+{
+    return ((size_t)((Ta + DTW_STRIP - 1) / DTW_STRIP) + 1) * (size_t)Tb * 64 * 8;
+}
+// waves of a launch over nc groups and np pairs: no more than its tiles can be
+static int align_waves(int64_t nc, int64_t np, int Ta, int Tb)
+{
+    const int64_t cap = std::max<int64_t>(1, (int64_t)(DTW_ALIGN_WAVE_CAP / align_wave_bytes(Ta, Tb)));
+    return (int)std::max<int64_t>(1, std::min<int64_t>(np / 64 + nc, std::min<int64_t>(DTW_WAVES, cap)));
+}
+static int64_t align_pair_chunk(int64_t P, int Ta, int F)
+{
+    return std::max<int64_t>(1, std::min<int64_t>(P, (int64_t)(DTW_ALIGN_RANGE_CAP / ((size_t)Ta * (8 + 8 * F)))));
+}
+
+// workspace: [code words and edges of G waves][padded a of one group chunk][lo, hi, S_k, d2 of one
+// pair chunk and cnt of one group chunk: dsp_dtw_dba_update only]
+struct AlignPlan {
+    int64_t nc, pc;
+    int G;
+    size_t waves, pad, ranges, sums, d2, cnt;
+    size_t total() const { return waves + pad + 2 * ranges + sums + d2 + cnt; }
+};
+static AlignPlan align_plan(int64_t Na, int64_t P, int Ta, int Tb, int F)
+{
+    AlignPlan pl;
+    pl.nc = std::max<int64_t>(1, std::min<int64_t>(Na, DTW_ALIGN_GCHUNK));
+    pl.pc = align_pair_chunk(P, Ta, F);
+    pl.G = align_waves(pl.nc, P, Ta, Tb);
+    pl.waves = up256((size_t)pl.G * align_wave_bytes(Ta, Tb));
+    pl.pad = up256((size_t)pl.nc * (Ta + DTW_STRIP) * F * 8);
+    pl.ranges = up256((size_t)pl.pc * Ta * 4);
+    pl.sums = up256((size_t)pl.pc * Ta * F * 8);
+    pl.d2 = up256((size_t)pl.pc * 8);
+    pl.cnt = up256((size_t)pl.nc * Ta * F * 4);
+    return pl;
+}
+
+// nc groups from group c0 on, their pairs in [p_lo, p_hi): the padded copy (pad = true), then the DP
+static int align_launch(hipStream_t s, const AlignPlan &pl, void *ws, bool pad, const double *a, const int32_t *len_a,
+                        int64_t c0, int64_t nc, int Ta, const double *b, const int32_t *len_b, int64_t Nb, int Tb,
+                        int F, int window, const int32_t *group_start, const int32_t *members, int64_t p_lo,
+                        int64_t p_hi, double *dist, double *d2, int32_t *lo, int32_t *hi)
+{
+    unsigned long long *dir = (unsigned long long *)ws;
+    const size_t dir_bytes = (size_t)pl.G * (size_t)((Ta + DTW_STRIP - 1) / DTW_STRIP) * Tb * 64 * 8;
+    double *edge = (double *)((char *)ws + dir_bytes);
+    double *apad = (double *)((char *)ws + pl.waves);
+    if (pad) {
+        const int64_t pad_elems = nc * (Ta + DTW_STRIP) * F;
+        hipLaunchKernelGGL(dtw_align_pad, dim3((unsigned)std::min<int64_t>((pad_elems + 255) / 256, 4096)), dim3(256),
+                           0, s, a + c0 * Ta * F, nc, Ta, F, apad);
+    }
+    const int G = std::min(pl.G, align_waves(nc, p_hi - p_lo, Ta, Tb));
+    const dim3 grid((unsigned)G), block(64);
+#define DTW_GO(FF)                                                                                                   \
+    case FF:                                                                                                         \
+        hipLaunchKernelGGL(dtw_align_dp<FF>, grid, block, 0, s, apad, len_a + c0, group_start + c0, (int)nc, Ta, b,  \
+                           len_b, Nb, Tb, members, (int)p_lo, (int)p_hi, window, dist, d2, lo, hi, edge, dir);       \
+        break;
+    switch (F) {
+        DTW_GO(1) DTW_GO(2) DTW_GO(3) DTW_GO(4) DTW_GO(5) DTW_GO(6) DTW_GO(7) DTW_GO(8)
+    default: return DSP_ERR_ARGS;
+    }
+#undef DTW_GO
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? DSP_OK : DSP_ERR_HIP + (int)e;
+}
+
+}  // namespace dsp
+
+extern "C" size_t dsp_dtw_align_workspace_bytes(int64_t Na, int64_t P, int Ta, int Tb, int F)
+{
+    if (!dsp::align_in_plan(Na, 0, P, Ta, Tb, F)) return 0;
+    return dsp::align_plan(Na, P, Ta, Tb, F).total();
+}
+
+extern "C" int dsp_dtw_align(const double *a, const int32_t *len_a, int64_t Na, int Ta, const double *b,
+                             const int32_t *len_b, int64_t Nb, int Tb, int F, int window,
+                             const int32_t *group_start, const int32_t *members, int64_t P, double *dist, int32_t *lo,
+                             int32_t *hi, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!dsp::align_in_plan(Na, Nb, P, Ta, Tb, F) || (lo == nullptr) != (hi == nullptr)) return DSP_ERR_ARGS;
+    if (Na == 0 || P == 0 || (!dist && !lo)) return DSP_OK;
+    if (!a || !len_a || !group_start || !members || (Nb > 0 && (!b || !len_b))) return DSP_ERR_ARGS;
+    const dsp::AlignPlan pl = dsp::align_plan(Na, P, Ta, Tb, F);
+    if (!workspace || workspace_bytes < pl.total()) return DSP_ERR_WORKSPACE;
+    for (int64_t c0 = 0; c0 < Na; c0 += pl.nc) {
+        const int rc = dsp::align_launch((hipStream_t)stream, pl, workspace, true, a, len_a, c0,
+                                         std::min(pl.nc, Na - c0), Ta, b, len_b, Nb, Tb, F, window, group_start,
+                                         members, 0, P, dist, nullptr, lo, hi);
+        if (rc != DSP_OK) return rc;
+    }
+    return DSP_OK;
+}
+
+extern "C" int dsp_dtw_dba_update(const double *tmpl, const int32_t *len_t, int64_t C, int Tt, const double *seqs,
+                                  const int32_t *len_s, int64_t N, int Ts, int F, int window,
+                                  const int32_t *group_start, const int32_t *members, int64_t P, double *tmpl_out,
+                                  double *inertia, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!dsp::align_in_plan(C, N, P, Tt, Ts, F)) return DSP_ERR_ARGS;
+    if (C == 0) return DSP_OK;
+    if (!tmpl || !len_t || !tmpl_out || tmpl_out == tmpl || !group_start || (P > 0 && !members) ||
+        (N > 0 && (!seqs || !len_s)))
+        return DSP_ERR_ARGS;
+    const dsp::AlignPlan pl = dsp::align_plan(C, P, Tt, Ts, F);
+    if (!workspace || workspace_bytes < pl.total()) return DSP_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    char *w = (char *)workspace + pl.waves + pl.pad;
+    int32_t *lo = (int32_t *)w, *hi = (int32_t *)(w + pl.ranges);
+    double *sums = (double *)(w + 2 * pl.ranges), *d2 = (double *)(w + 2 * pl.ranges + pl.sums);
+    int32_t *cnt = (int32_t *)(w + 2 * pl.ranges + pl.sums + pl.d2);
+    for (int64_t c0 = 0; c0 < C; c0 += pl.nc) {
+        const int64_t nc = std::min(pl.nc, C - c0), elems = nc * Tt * F;
+        const dim3 grid((unsigned)std::min<int64_t>((elems + 255) / 256, 65536)), block(256);
+        double *out = tmpl_out + c0 * Tt * F, *in = inertia ? inertia + c0 : nullptr;
+        hipLaunchKernelGGL(dsp::dba_begin, grid, block, 0, s, cnt, elems);
+        for (int64_t p_lo = 0; p_lo < P; p_lo += pl.pc) {
+            const int64_t p_hi = std::min(P, p_lo + pl.pc);
+            const int rc = dsp::align_launch(s, pl, workspace, p_lo == 0, tmpl, len_t, c0, nc, Tt, seqs, len_s, N, Ts,
+                                             F, window, group_start, members, p_lo, p_hi, nullptr, d2, lo, hi);
+            if (rc != DSP_OK) return rc;
+            const int64_t selems = (p_hi - p_lo) * Tt * F;
+            hipLaunchKernelGGL(dsp::dba_sums, dim3((unsigned)std::min<int64_t>((selems + 255) / 256, 65536)), block, 0, s,
+                               seqs, N, Ts, F, Tt, group_start + c0, (int)nc, members, (int)p_lo, (int)p_hi, lo, hi, sums);
+            hipLaunchKernelGGL(dsp::dba_accumulate, grid, block, 0, s, F, group_start + c0, (int)nc, Tt, len_t + c0,
+                               (int)p_lo, (int)p_hi, lo, hi, sums, d2, out, cnt, in);
+        }
+        hipLaunchKernelGGL(dsp::dba_finish, grid, block, 0, s, tmpl + c0 * Tt * F, len_t + c0, (int)nc, Tt, F, cnt, out,
+                           in);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return DSP_ERR_HIP + (int)e;
+    }
+    return DSP_OK;
+}

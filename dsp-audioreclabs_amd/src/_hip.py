@@ -38,7 +38,7 @@ EXPORTS = ("dsp_extract_lds_bytes", "dsp_extract_fast_layout", "dsp_extract_feat
            "dsp_svc_workspace_uncertified_offset", "dsp_svc_launch_parts", "dsp_svc_predict",
            "dsp_gnb_fit", "dsp_gnb_workspace_bytes", "dsp_gnb_predict", "dsp_tree_workspace_bytes",
            "dsp_tree_lds_nodes", "dsp_tree_predict", "dsp_dtw_workspace_bytes", "dsp_dtw_pairwise",
-           "dsp_dtw_knn")
+           "dsp_dtw_knn", "dsp_dtw_align_workspace_bytes", "dsp_dtw_align", "dsp_dtw_dba_update")
 DSP_WAV_OTHER, DSP_WAV_S16_MONO, DSP_WAV_U8_MONO = 0, 1, 2
 
 _lib = None
@@ -146,6 +146,13 @@ def load_library(path=LIB_PATH):
         L.dsp_dtw_knn.restype = i32
         L.dsp_dtw_knn.argtypes = [vp, vp, vp, i64, i32, vp, vp, i64, i32, i32, i32, i32, i64, i32, vp, vp, vp,
                                   vp, sz, vp]
+    if hasattr(L, "dsp_dtw_align"):  # (older A/B variants lack the alignment paths and the DBA)
+        L.dsp_dtw_align_workspace_bytes.restype = sz
+        L.dsp_dtw_align_workspace_bytes.argtypes = [i64, i64, i32, i32, i32]
+        L.dsp_dtw_align.restype = i32
+        L.dsp_dtw_align.argtypes = [vp, vp, i64, i32, vp, vp, i64, i32, i32, i32, vp, vp, i64, vp, vp, vp, vp, sz, vp]
+        L.dsp_dtw_dba_update.restype = i32
+        L.dsp_dtw_dba_update.argtypes = [vp, vp, i64, i32, vp, vp, i64, i32, i32, i32, vp, vp, i64, vp, vp, vp, sz, vp]
     _lib = L
     return L
 

@@ -29,6 +29,8 @@ walks the fitted tree on the device (csrc/tree.hip, dsp_tree_predict): compariso
 ``SequenceClassifier`` / ``create_classifier('dtw_knn')`` (an extension: the reference has no
 sequence classifier) is k-NN under dynamic time warping on the per-frame sequences (csrc/dtw.hip,
 dsp_dtw_knn): an exact fp64 distance, the KNN's voting and tie rules.
+``TemplateClassifier`` / ``create_classifier('dtw_template')`` keeps one DBA template per class instead
+of the training set (csrc/dtw_align.hip, dsp_dtw_dba_update).
 
 ``MLPTrainer`` (models.py:109-221) trains the reference's MLP with the fused on-device trainer
 (csrc/mlp.hip: dsp_mlp_train / dsp_mlp_predict) -- the whole serial SGD loop of
@@ -289,7 +291,8 @@ class SequenceClassifier:
         out[~valid] = 0.0
         return out
 
-    def fit(self, X, y, lengths=None):
+    def _training_set(self, X, y, lengths):
+        """(scaled padded X, lengths, class codes) of a training set; sets mean_, std_ and classes_."""
         X, n = _as_padded(X, lengths)
         y = np.asarray(y)
         if len(y) != len(X):
@@ -304,7 +307,10 @@ class SequenceClassifier:
             self.std_ = np.where(std == 0, 1.0, std)
         # classes_ sorted as in scikit-learn: the vote's smallest-index tie break is the smallest label
         self.classes_, codes = np.unique(y, return_inverse=True)
-        self._fit_X, self._fit_n, self._codes = self._scale(X, n), n, codes.astype(np.int32)
+        return self._scale(X, n), n, codes.astype(np.int32)
+
+    def fit(self, X, y, lengths=None):
+        self._fit_X, self._fit_n, self._codes = self._training_set(X, y, lengths)
         self._index = None  # uploaded at the first query
         return self
 
@@ -336,6 +342,61 @@ class SequenceClassifier:
             'classification_report': classification_report(y, y_pred, output_dict=True, zero_division=0),
             'confusion_matrix': confusion_matrix(y, y_pred),
         }
+
+
+def medoid_index(cost_rows):
+    """The medoid rule on the candidates' squared-distance rows d * d [n_candidates, M]: the cost of
+    a candidate is the sequential sum over the members in order (cumsum), the smallest wins, ties go
+    to the earliest candidate."""
+    return int(np.argmin(np.cumsum(cost_rows, axis=1)[:, -1]))
+
+
+class TemplateClassifier(SequenceClassifier):
+    """Template matching, the classical form of the isolated-word recogniser: one reference pattern
+    per class, the class's DTW barycentre (DBA; Petitjean, Ketterlin, Gancarski 2011), and the label of
+    the nearest template under DTW.  csrc/dtw_align.hip (dsp_dtw_dba_update).  Input
+    handling and normalisation are ``SequenceClassifier``'s; prediction is its 1-NN over the templates
+    (``n_classes`` dynamic programmes per query instead of one per training sequence).
+
+    n_iter             DBA updates, all classes in each call.
+    medoid_candidates  each class starts from its medoid among the first ``medoid_candidates`` members
+                       (training order): the candidate with the smallest sum of squared DTW distances
+                       to all members of the class (``medoid_index``).
+    After ``fit``: templates_ float64 [C, T, F] (normalised units, zeros behind each length),
+    template_lengths_ int32 [C], inertia_ float64 [n_iter, C] (row t: each class's sum of squared DTW
+    distances to the template that update t started from).
+    No CPU path: ``fit`` and ``predict`` raise HipError without a HIP device (constructing needs none).
+    """
+
+    def __init__(self, n_iter=10, window=None, normalize=True, medoid_candidates=256):
+        super().__init__(n_neighbors=1, window=window, normalize=normalize)
+        self.n_iter, self.medoid_candidates = int(n_iter), int(medoid_candidates)
+        if self.n_iter < 0 or self.medoid_candidates < 1:
+            raise ValueError("n_iter must be >= 0 and medoid_candidates >= 1")
+
+    def fit(self, X, y, lengths=None):
+        from .pipeline import DbaUpdater, dtw_pairwise
+        X, n, codes = self._training_set(X, y, lengths)
+        C = len(self.classes_)
+        order = np.argsort(codes, kind="stable")  # each class's members in training order
+        start = np.concatenate([[0], np.cumsum(np.bincount(codes, minlength=C))])
+        medoids = []
+        for c in range(C):
+            mem = order[start[c]:start[c + 1]]
+            cand = mem[:self.medoid_candidates]
+            d = dtw_pairwise(X[cand], n[cand], X[mem], n[mem], window=self.window, check_finite=False).cpu().numpy()
+            medoids.append(cand[medoid_index(d * d)])
+        tmpl, len_t = X[medoids], n[medoids]
+        updater = DbaUpdater(X, n, start, order, window=self.window, check_finite=False)
+        inertia = np.zeros((self.n_iter, C))
+        for t in range(self.n_iter):
+            tmpl, inert = updater.update(tmpl, len_t)
+            inertia[t] = inert.cpu().numpy()
+        self.templates_ = tmpl.cpu().numpy() if hasattr(tmpl, 'cpu') else tmpl
+        self.template_lengths_, self.inertia_ = len_t.astype(np.int32), inertia
+        self._fit_X, self._fit_n, self._codes = self.templates_, self.template_lengths_, np.arange(C, dtype=np.int32)
+        self._index = None  # uploaded at the first query
+        return self
 
 
 # ==================== MLP (models.py:77-221) ====================
@@ -604,13 +665,15 @@ def fit_mlp_models(X_train, y_train, input_size, hidden_layers, num_classes, lea
 
 
 def create_classifier(classifier_type, **kwargs):
-    """models.py:226-246.  'mlp' takes MLPTrainer's arguments; 'dtw_knn' (an extension) is the
-    SequenceClassifier.  A bare ``create_classifier('mlp')``
+    """models.py:226-246.  'mlp' takes MLPTrainer's arguments; 'dtw_knn' and 'dtw_template' (extensions) are the
+    SequenceClassifier and the TemplateClassifier.  A bare ``create_classifier('mlp')``
     raises NotImplementedError naming them (the reference fails there with a TypeError)."""
     if classifier_type in ['knn', 'naive_bayes', 'decision_tree', 'svm']:
         return TraditionalClassifier(classifier_type, **kwargs)
     if classifier_type == 'dtw_knn':
         return SequenceClassifier(**kwargs)
+    if classifier_type == 'dtw_template':
+        return TemplateClassifier(**kwargs)
     if classifier_type == 'mlp':
         if not kwargs:
             raise NotImplementedError("create_classifier('mlp') needs input_size, hidden_layers and num_classes "

@@ -334,6 +334,133 @@ class DtwIndex:
         return idx, dist, pred
 
 
+def _dtw_groups(groups, assign, Na, Nb):
+    """The CSR pair list (group_start int32 [Na + 1], members int32 [P]) on the host, from the
+    pair itself or from ``assign`` [Nb] (the a index of each b sequence, -1 to skip; a stable sort, so
+    a group lists its members in ascending order)."""
+    if (groups is None) == (assign is None):
+        raise ValueError("pass either groups=(group_start, members) or assign")
+    if assign is not None:
+        assign = np.asarray(assign.cpu().numpy() if hasattr(assign, "cpu") else assign).astype(np.int64).reshape(-1)
+        if assign.size != Nb or (assign.size and (assign.min() < -1 or assign.max() >= Na)):
+            raise ValueError("assign must hold one index in [-1, %d) per b sequence" % Na)
+        members = np.flatnonzero(assign >= 0)
+        members = members[np.argsort(assign[members], kind="stable")]
+        start = np.concatenate([[0], np.cumsum(np.bincount(assign[members], minlength=Na))])
+    else:
+        start, members = (np.asarray(g.cpu().numpy() if hasattr(g, "cpu") else g).astype(np.int64).reshape(-1)
+                          for g in groups)
+        if start.size != Na + 1 or start[0] != 0 or (np.diff(start) < 0).any() or start[-1] != members.size:
+            raise ValueError("group_start must be [Na + 1], non-decreasing from 0 to len(members)")
+    return start.astype(np.int32), members.astype(np.int32)
+
+
+def dtw_align(a, len_a, b, len_b, groups=None, assign=None, window=None, with_ranges=True, check_finite=True):
+    """DTW alignment paths (include/dsp_audiorec.h: dsp_dtw_align) of the padded sequences
+    b[members[p]] to a[c], the pairs given as the CSR ``groups=(group_start [Na + 1], members [P])`` or
+    as ``assign`` [Nb].  Returns (dist float64 [P], lo, hi int32 [P, Ta] or None, group_start, members)
+    on the device: frame i of a is matched to frames lo[i] .. hi[i] of b (-1 past a's length)."""
+    import torch
+    d = _hip.require_device()
+    a, len_a = _dtw_operand(a, len_a, d, check_finite)
+    b, len_b = _dtw_operand(b, len_b, d, check_finite)
+    (Na, Ta, F), (Nb, Tb, Fb) = a.shape, b.shape
+    if F != Fb:
+        raise ValueError("sequences of %d and %d feature channels" % (F, Fb))
+    start, members = _dtw_groups(groups, assign, Na, Nb)
+    P = int(members.size)
+    start, members = _as_device(start, torch.int32, d), _as_device(members, torch.int32, d)
+    dist = torch.empty(P, dtype=torch.float64, device=d)
+    lo = torch.empty((P, Ta), dtype=torch.int32, device=d) if with_ranges else None
+    hi = torch.empty((P, Ta), dtype=torch.int32, device=d) if with_ranges else None
+    if P > 0:
+        nbytes = _hip.lib().dsp_dtw_align_workspace_bytes(Na, P, Ta, Tb, F)
+        if nbytes == 0:
+            raise ValueError("unsupported DTW shape (1 <= F <= 8, 1 <= T <= 1024)")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=d)
+        rc = _hip.lib().dsp_dtw_align(_hip.ptr(a), _hip.ptr(len_a), Na, Ta, _hip.ptr(b), _hip.ptr(len_b), Nb, Tb, F,
+                                      _dtw_window(window), _hip.ptr(start), _hip.ptr(members), P, _hip.ptr(dist),
+                                      _hip.ptr(lo), _hip.ptr(hi), _hip.ptr(ws), nbytes, _hip.stream_handle(d))
+        _hip.check(rc, "dsp_dtw_align")
+    return dist, lo, hi, start, members
+
+
+def dtw_path(x, y, window=None):
+    """The warping path of one pair of [n, F] / [m, F] arrays: (distance, path int64 [L, 2]), the
+    cells (i, j) ascending from (0, 0) to (n-1, m-1), expanded on the host from dsp_dtw_align's ranges."""
+    x, y = (np.asarray(v.cpu().numpy() if hasattr(v, "cpu") else v, dtype=np.float64) for v in (x, y))
+    x, y = (v.reshape(-1, 1) if v.ndim == 1 else v for v in (x, y))
+    if x.ndim != 2 or y.ndim != 2 or len(x) < 1 or len(y) < 1:
+        raise ValueError("x and y must be non-empty [n, F] arrays")
+    dist, lo, hi, _, _ = dtw_align(x[None], [len(x)], y[None], [len(y)], groups=([0, 1], [0]), window=window)
+    lo, hi = lo[0].cpu().numpy().astype(np.int64), hi[0].cpu().numpy().astype(np.int64)
+    count = hi - lo + 1
+    i = np.repeat(np.arange(len(x)), count)
+    j = np.arange(count.sum()) - np.repeat(np.cumsum(count) - count, count) + np.repeat(lo, count)
+    return float(dist[0].item()), np.stack([i, j], axis=1)
+
+
+class DbaUpdater:
+    """The sequences of a DBA run uploaded once with their CSR class lists; ``update`` is one
+    ``dsp_dtw_dba_update`` call for all templates: (new templates [C, Tt, F], inertia [C]) on the
+    device."""
+
+    def __init__(self, seqs, lengths, group_start, members, window=None, check_finite=True):
+        import torch
+        self.device = d = _hip.require_device()
+        self.seqs, self.len_s = _dtw_operand(seqs, lengths, d, check_finite)
+        self.N, self.Ts, self.F = self.seqs.shape
+        self.C = len(group_start) - 1
+        self.start, self.members = _dtw_groups((group_start, members), None, self.C, self.N)
+        self.P = int(self.members.size)
+        self.start, self.members = _as_device(self.start, torch.int32, d), _as_device(self.members, torch.int32, d)
+        self.window = _dtw_window(window)
+        self._ws = None
+
+    def update(self, tmpl, len_t):
+        import torch
+        d = self.device
+        tmpl, len_t = _dtw_operand(tmpl, len_t, d, False)
+        C, Tt, F = tmpl.shape
+        if C != self.C or F != self.F:
+            raise ValueError("templates [%d, ., %d] for %d classes of %d channels" % (C, F, self.C, self.F))
+        nbytes = _hip.lib().dsp_dtw_align_workspace_bytes(C, self.P, Tt, self.Ts, F)
+        if nbytes == 0:
+            raise ValueError("unsupported DTW shape (1 <= F <= 8, 1 <= T <= 1024)")
+        if self._ws is None or self._ws.numel() < nbytes:
+            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=d)
+        out = torch.empty_like(tmpl)
+        inertia = torch.empty(C, dtype=torch.float64, device=d)
+        rc = _hip.lib().dsp_dtw_dba_update(_hip.ptr(tmpl), _hip.ptr(len_t), C, Tt, _hip.ptr(self.seqs),
+                                           _hip.ptr(self.len_s), self.N, self.Ts, F, self.window, _hip.ptr(self.start),
+                                           _hip.ptr(self.members), self.P, _hip.ptr(out), _hip.ptr(inertia),
+                                           _hip.ptr(self._ws), self._ws.numel(), _hip.stream_handle(d))
+        _hip.check(rc, "dsp_dtw_dba_update")
+        return out, inertia
+
+
+def dtw_barycenter(seqs, lengths, init, n_iter=10, window=None, check_finite=True):
+    """DTW barycentre averaging of the padded sequences [N, T, F] from the template ``init`` [L, F]:
+    (template float64 [L, F], inertia float64 [iterations run]) as numpy arrays, inertia[t] the sum of
+    squared DTW distances to the template that iteration t started from.  Stops early when an update
+    returns the template bitwise unchanged; the result then equals running all ``n_iter``."""
+    import torch
+    init = np.asarray(init.cpu().numpy() if hasattr(init, "cpu") else init, dtype=np.float64)
+    init = init.reshape(-1, 1) if init.ndim == 1 else init
+    N = len(lengths)
+    up = DbaUpdater(seqs, lengths, [0, N], np.arange(N), window, check_finite)
+    tmpl = _as_device(init[None], torch.float64, up.device)
+    inertia = []
+    for _ in range(int(n_iter)):
+        new, inert = up.update(tmpl, [len(init)])
+        inertia.append(float(inert[0].item()))
+        same = bool(torch.equal(new.view(torch.int64), tmpl.view(torch.int64)))
+        tmpl = new
+        if same:
+            break
+    return tmpl[0].cpu().numpy(), np.array(inertia)
+
+
 class SvcIndex:
     """A fitted ``sklearn.svm.SVC(kernel='rbf')`` uploaded once for ``dsp_svc_predict``
     (csrc/svm.hip): libsvm's own arrays -- support_vectors_, _n_support, _dual_coef_, _intercept_,

@@ -36,7 +36,7 @@ extern "C" {
                               5: queue_ws is 4 KiB (each counter on its own 256-B line);
                               6: the extraction entry points take out_stride (packed result rows);
                                  dsp_knn_classify takes flags (DSP_KNN_REF_READY).
-                              Still 6 with the dsp_mlp_*, dsp_svc_*, dsp_gnb_*, dsp_tree_* and dsp_dtw_* entry points: new symbols only, no
+                              Still 6 with the dsp_mlp_*, dsp_svc_*, dsp_gnb_*, dsp_tree_* and dsp_dtw_* (dsp_dtw_align, dsp_dtw_dba_update included) entry points: new symbols only, no
                               existing signature or meaning changed, so callers built against 6 keep
                               working (a binding that needs them checks for the symbols) */
 
@@ -436,6 +436,60 @@ int dsp_dtw_knn(const double *ref, const int32_t *len_ref, const int32_t *ref_la
                 const double *query, const int32_t *len_query, int64_t Nq, int Tq, int F, int window,
                 int k, int64_t self_offset, int n_classes, int32_t *idx, double *dist, int32_t *pred,
                 void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * DTW alignment paths and one DTW barycentre averaging (DBA; Petitjean, Ketterlin, Gancarski 2011)
+ * update on them.  csrc/dtw_align.hip, DESIGN.md §4.9.  c, D, the band, the plan (1 <= F <= 8,
+ * 1 <= T <= 1024) and invalid lengths are those above, unchanged.
+ *
+ * Path.  For a pair with lengths n (side a, index i) and m (side b, index j) the path is found by
+ * walking back from (n-1, m-1) to (0, 0): the predecessor of (i, j) is the first of (i-1, j-1),
+ * (i-1, j), (i, j-1) whose D equals the minimum of the three; neighbours outside the grid or the
+ * band count as +inf.  D is defined bit for bit, so the path is.  dtw(a, b) and dtw(b, a) have equal
+ * bits, but the tie rule is stated in a / b indices and is NOT symmetric.
+ * Ranges.  The path is returned from a's side as two int32 rows per pair: frame i of a is matched to
+ * frames lo[i] .. hi[i] of b.  lo[0] = 0, hi[n-1] = m-1 and hi[i] <= lo[i+1] <= hi[i] + 1; the
+ * path's cells are exactly {(i, j): lo[i] <= j <= hi[i]}.  Entries i >= n are -1.  A pair with an
+ * invalid length on either side gives dist = +inf and all entries -1.
+ * Pairs are a CSR list over a: group_start int32 [Na + 1] (non-decreasing, group_start[0] = 0),
+ * members int32 [P], P = group_start[Na] passed by the host (P < 2^31).  The sequences aligned to
+ * a[c] are b[members[p]] for p in [group_start[c], group_start[c+1]); outputs are indexed by p.  A b
+ * sequence may appear under several a's; a group may be empty.  A members entry outside [0, Nb) is
+ * treated as an invalid length and never read through.
+ *
+ * dsp_dtw_align: dist float64 [P] (the dtw value of dsp_dtw_pairwise; may be NULL), lo and hi int32
+ *   [P, Ta] (both or neither NULL; without them no path is walked).
+ * dsp_dtw_dba_update: one DBA iteration for all templates in one call.  tmpl [C, Tt, F] with len_t,
+ *   seqs [N, Ts, F] with len_s, the CSR list over the templates.  For template c of length L with
+ *   valid-length members k0 < k1 < ... in list order:
+ *     S_k[i,f] = s_k[lo,f] + s_k[lo+1,f] + ... + s_k[hi,f]     left to right, each sum rounded
+ *     acc[i,f] = S_k0[i,f];  acc = acc + S_k for k1, k2, ...   in list order
+ *     cnt[i]   = sum_k (hi - lo + 1)                           integer
+ *     new[i,f] = acc[i,f] / (double)cnt[i]                     one rounded division
+ *     inertia  = D_k0(end);  inertia = inertia + D_k(end)      dtw^2 (before the sqrt), in list order
+ *   with lo, hi the ranges of the pair (template c, member k).  Rows i >= L of tmpl_out [C, Tt, F]
+ *   are zeros.  tmpl_out[c] is a bitwise copy of tmpl[c] and its inertia 0.0 when the template's own
+ *   length is invalid or it has no valid member; members with an invalid length are skipped.
+ *   inertia float64 [C] may be NULL.  tmpl_out must not be tmpl.
+ * workspace  device scratch of dsp_dtw_align_workspace_bytes(Na, P, Ta, Tb, F) bytes for both (C, Tt, Ts
+ *   for Na, Ta, Tb; 0: sizes outside the plan).  It stays bounded whatever Na and P are: per
+ *   resident wave (at most 4096, and at most 1 GiB of them) the predecessor codes of one tile --
+ *   ceil(Ta / 32) x Tb x 64 words of 8 bytes -- and its edge column; the padded copy of one chunk of
+ *   at most 1024 a sequences; and, for the DBA, the ranges and the sums S_k of one chunk of pairs
+ *   (at most 128 MiB together) and the counts of one chunk of templates.
+ * Both check their host arguments before any launch (DSP_ERR_ARGS, DSP_ERR_WORKSPACE), return DSP_OK
+ * with nothing to do, make no host synchronisation and no allocation, and write only to their
+ * outputs and the workspace, on the caller's stream.
+ */
+size_t dsp_dtw_align_workspace_bytes(int64_t Na, int64_t P, int Ta, int Tb, int F);
+int dsp_dtw_align(const double *a, const int32_t *len_a, int64_t Na, int Ta, const double *b,
+                  const int32_t *len_b, int64_t Nb, int Tb, int F, int window, const int32_t *group_start,
+                  const int32_t *members, int64_t P, double *dist, int32_t *lo, int32_t *hi, void *workspace,
+                  size_t workspace_bytes, void *stream);
+int dsp_dtw_dba_update(const double *tmpl, const int32_t *len_t, int64_t C, int Tt, const double *seqs,
+                       const int32_t *len_s, int64_t N, int Ts, int F, int window, const int32_t *group_start,
+                       const int32_t *members, int64_t P, double *tmpl_out, double *inertia, void *workspace,
+                       size_t workspace_bytes, void *stream);
 
 /*
  * Batch WAV reader -- host only (no GPU, no stream): the file side of load_wav

@@ -19,7 +19,17 @@ Baseline: the vectorised numpy restatement of tests/dtw_reference.py on a 1/100 
 (every 100th query against all references) on this host, scaled by 100.  It is the only other
 implementation of this distance that exists here (no dtaidistance, no tslearn); it is a reference
 written for clarity, not a tuned CPU DTW.  The sampled queries' neighbours and distances are also
-compared with the device's, bit for bit.  Prints one JSON document and writes it to --out."""
+compared with the device's, bit for bit.  Prints one JSON document and writes it to --out.
+
+--legs template [--template-out profiles/dtw_template_bench.json] [--n-iter 10] [--labelled-clips 2000]:
+the unconstrained leg above (the yardstick of the same run) and beside it the DBA template classifier
+(csrc/dtw_align.hip) on the same split, its classes the legs' pseudo labels (clip
+index mod 10).  fit, split into the medoid search and each ``dsp_dtw_dba_update`` (and that call
+alone on buffers made once); the align DP's admissible cells/s, distances only and with the paths
+walked and written, on the fit's own pair list and at the k-NN leg's shape (every reference under
+each of the first 250 queries, its distances checked against dsp_dtw_pairwise's bits); predict
+against the templates; and, since the device-synthesised clips carry no classes, the accuracy of
+``dtw_template`` against ``dtw_knn`` on --labelled-clips host-synthesised labelled clips split 80 / 20."""
 import argparse
 import json
 import os
@@ -128,20 +138,204 @@ def leg(x, lens, cut, window, replays, sample):
     return r
 
 
+def timed(fn, replays, warmup=2):
+    """(last result, [ms per call]) of fn under device events after ``warmup`` untimed calls."""
+    for _ in range(warmup):
+        out = fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(replays):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = fn()
+        e1.record()
+        torch.cuda.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    return out, ms
+
+
+def labelled_sequences(n_clips, dev):
+    """Unpadded (E, ZCR) float64 sequences of host-synthesised clips whose f0 and duration depend on one
+    of 10 labels (src.synth.make_batch): the device-synthesised clips of the timing legs carry none."""
+    from src.pipeline import FeatureExtractor
+    from src.synth import make_batch
+    fx = FeatureExtractor(1102, 441, "hamming", True, return_sequences=True)
+    seqs, ys = [], []
+    for lo in range(0, n_clips, 1024):
+        pcm, y = make_batch(min(1024, n_clips - lo), start=lo, with_labels=True)
+        out = fx(torch.as_tensor(pcm, device=dev))
+        ok = ((out["status"] & 0xFF) == 0).cpu().numpy()
+        seq, n = out["seq"].cpu().numpy(), out["n_frames"].cpu().numpy()
+        seqs += [seq[i, :n[i]][:, [0, 2]].astype(np.float64) for i in np.flatnonzero(ok)]
+        ys.append(y[ok])
+    return seqs, np.concatenate(ys)
+
+
+def template_leg(x, lens, cut, knn_leg, replays, n_iter, labelled_clips):
+    """The DBA template classifier on the split of the k-NN legs (the classes are the legs' pseudo
+    labels, clip index mod 10: timing does not depend on what a class means), then its accuracy
+    against dtw_knn on a labelled corpus."""
+    from src.models import SequenceClassifier, TemplateClassifier, medoid_index
+    from src.pipeline import DbaUpdater, DtwIndex, dtw_align, dtw_pairwise
+    dev, F = x.device, x.shape[2]
+    ref, lr, qs, lq = x[:cut], lens[:cut], x[cut:], lens[cut:]
+    codes = (torch.arange(cut) % 10).numpy()
+    C = 10
+    order = np.argsort(codes, kind="stable")
+    start = np.concatenate([[0], np.cumsum(np.bincount(codes, minlength=C))])
+    order_t = torch.as_tensor(order, device=dev)
+
+    # fit, phase 1: the medoid of each class among its first 256 members (TemplateClassifier.fit's loop)
+    def medoids():
+        out = []
+        for c in range(C):
+            mem = order_t[start[c]:start[c + 1]]
+            cand = mem[:256]
+            d = dtw_pairwise(ref[cand], lr[cand], ref[mem], lr[mem], check_finite=False).cpu().numpy()
+            out.append(int(cand[medoid_index(d * d)].item()))
+        return out
+
+    medoids()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    med = medoids()
+    torch.cuda.synchronize()
+    medoid_ms = (time.perf_counter() - t0) * 1e3
+    medoid_cells = int(sum(int(lr[order_t[start[c]:start[c + 1]][:256]].sum().item()) *
+                           int(lr[order_t[start[c]:start[c + 1]]].sum().item()) for c in range(C)))
+    # fit, phase 2: n_iter updates of all classes, each one call
+    up = DbaUpdater(ref, lr, start, order, check_finite=False)
+    tmpl, len_t = ref[med].contiguous(), lr[med].contiguous()
+    up.update(tmpl, len_t)
+    torch.cuda.synchronize()
+    update_ms, inertia = [], []
+    for _ in range(n_iter):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        tmpl, inert = up.update(tmpl, len_t)
+        e1.record()
+        torch.cuda.synchronize()
+        update_ms.append(e0.elapsed_time(e1))
+        inertia.append(float(inert.sum().item()))
+    # the align DP alone on the last update's pairs: distances only, and with the walk back
+    lt_np, lr_np = len_t.cpu().numpy().astype(np.int64), lr.cpu().numpy().astype(np.int64)
+    cells = int(sum(lt_np[c] * lr_np[order[start[c]:start[c + 1]]].sum() for c in range(C)))
+    # (the bare entry point on buffers made once: nothing but the call's own launches between the events)
+    from src import _hip
+    lib, P, Tt = _hip.lib(), len(order), tmpl.shape[1]
+    st, mem = torch.as_tensor(start, dtype=torch.int32, device=dev), torch.as_tensor(order, dtype=torch.int32, device=dev)
+    dist = torch.empty(P, dtype=torch.float64, device=dev)
+    lo, hi = (torch.empty((P, Tt), dtype=torch.int32, device=dev) for _ in range(2))
+    nbytes = lib.dsp_dtw_align_workspace_bytes(C, P, Tt, ref.shape[1], F)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+    def align_call(ranges):
+        _hip.check(lib.dsp_dtw_align(_hip.ptr(tmpl), _hip.ptr(len_t), C, Tt, _hip.ptr(ref), _hip.ptr(lr), cut,
+                                     ref.shape[1], F, -1, _hip.ptr(st), _hip.ptr(mem), P, _hip.ptr(dist),
+                                     _hip.ptr(lo) if ranges else None, _hip.ptr(hi) if ranges else None,
+                                     _hip.ptr(ws), nbytes, _hip.stream_handle(dev)), "dsp_dtw_align")
+
+    _, dist_ms = timed(lambda: align_call(False), replays)
+    _, path_ms = timed(lambda: align_call(True), replays)
+    out_t, out_i = torch.empty_like(tmpl), torch.empty(C, dtype=torch.float64, device=dev)
+
+    def update_call():  # one update's launches, without the Python around them
+        _hip.check(lib.dsp_dtw_dba_update(_hip.ptr(tmpl), _hip.ptr(len_t), C, Tt, _hip.ptr(ref), _hip.ptr(lr), cut,
+                                          ref.shape[1], F, -1, _hip.ptr(st), _hip.ptr(mem), P, _hip.ptr(out_t),
+                                          _hip.ptr(out_i), _hip.ptr(ws), nbytes, _hip.stream_handle(dev)),
+                   "dsp_dtw_dba_update")
+
+    _, bare_ms = timed(update_call, replays)
+    got = dtw_align(tmpl, len_t, ref, lr, groups=(start, order), check_finite=False)
+    assert torch.equal(got[0], dist) and torch.equal(got[1], lo) and torch.equal(got[2], hi)
+    # The fit's pair list is 130 tiles, less than one per CU: it times launches, not the DP.  The DP's
+    # rate is measured at the k-NN leg's own shape, full 64-lane tiles of every reference under each
+    # query, on the first `nqa` queries (the ranges of all 2 000 would be 4 GB).
+    nqa = min(250, qs.shape[0])
+    Pa, Tq = nqa * cut, qs.shape[1]
+    sta = torch.arange(nqa + 1, dtype=torch.int32, device=dev) * cut
+    mema = torch.arange(cut, dtype=torch.int32, device=dev).repeat(nqa)
+    dista = torch.empty(Pa, dtype=torch.float64, device=dev)
+    loa, hia = (torch.empty((Pa, Tq), dtype=torch.int32, device=dev) for _ in range(2))
+    nba = lib.dsp_dtw_align_workspace_bytes(nqa, Pa, Tq, ref.shape[1], F)
+    wsa = torch.empty(nba, dtype=torch.uint8, device=dev)
+    qa, lqa = qs[:nqa].contiguous(), lq[:nqa].contiguous()
+
+    def align_full(ranges):
+        _hip.check(lib.dsp_dtw_align(_hip.ptr(qa), _hip.ptr(lqa), nqa, Tq, _hip.ptr(ref), _hip.ptr(lr), cut,
+                                     ref.shape[1], F, -1, _hip.ptr(sta), _hip.ptr(mema), Pa, _hip.ptr(dista),
+                                     _hip.ptr(loa) if ranges else None, _hip.ptr(hia) if ranges else None,
+                                     _hip.ptr(wsa), nba, _hip.stream_handle(dev)), "dsp_dtw_align")
+
+    _, fdist_ms = timed(lambda: align_full(False), replays)
+    _, fpath_ms = timed(lambda: align_full(True), replays)
+    fcells = int(lqa.sum().item()) * int(lr_np.sum())
+    pw = dtw_pairwise(qa, lqa, ref, lr, check_finite=False)
+    assert torch.equal(pw.reshape(-1), dista)  # the distances are dsp_dtw_pairwise's bits
+    fd, fp = float(np.median(fdist_ms)), float(np.median(fpath_ms))
+    # predict: dsp_dtw_knn with the templates as its references, a tile per query with C of 64 lanes in use
+    index = DtwIndex(tmpl, len_t, torch.arange(C, dtype=torch.int32), 1, n_classes=C, check_finite=False)
+    _, predict_ms = timed(lambda: index.query(qs, lq, check_finite=False), replays)
+    pcells = int(lq.sum().item()) * int(lt_np.sum())
+    med_d, med_p, med_q = float(np.median(dist_ms)), float(np.median(path_ms)), float(np.median(predict_ms))
+    r = dict(leg="dtw_template", classes=C, n_iter=n_iter, Nr=int(cut), Nq=int(qs.shape[0]), F=F,
+             template_lengths=lt_np.tolist(), fit_medoid_ms=medoid_ms, fit_medoid_cells=medoid_cells,
+             fit_update_ms=update_ms, fit_update_ms_median=float(np.median(update_ms)),
+             fit_total_ms=medoid_ms + float(np.sum(update_ms)), inertia_per_iteration=inertia,
+             update_call_alone_ms=float(np.median(bare_ms)),
+             align_pairs=int(len(order)), align_cells=cells,
+             align_dist_only_ms=med_d, align_dist_only_cells_per_s=cells / (med_d * 1e-3),
+             align_with_paths_ms=med_p, align_with_paths_cells_per_s=cells / (med_p * 1e-3),
+             align_full_queries=nqa, align_full_pairs=Pa, align_full_cells=fcells,
+             align_full_dist_only_ms=fd, align_full_dist_only_cells_per_s=fcells / (fd * 1e-3),
+             align_full_with_paths_ms=fp, align_full_with_paths_cells_per_s=fcells / (fp * 1e-3),
+             knn_unconstrained_cells_per_s=knn_leg["cells_per_s"],
+             align_full_dist_only_over_knn=fcells / (fd * 1e-3) / knn_leg["cells_per_s"],
+             align_full_with_paths_over_knn=fcells / (fp * 1e-3) / knn_leg["cells_per_s"],
+             predict_ms=med_q, predict_cells=pcells, predict_cells_per_s=pcells / (med_q * 1e-3),
+             predict_lanes_used_of_64=C, knn_predict_ms=knn_leg["ms_median"],
+             predict_speedup_over_knn=knn_leg["ms_median"] / med_q, replays=replays)
+    # accuracy on clips that have classes
+    seqs, y = labelled_sequences(labelled_clips, dev)
+    cut2 = len(seqs) * 8 // 10
+    t0 = time.perf_counter()
+    tc = TemplateClassifier(n_iter=n_iter).fit(seqs[:cut2], y[:cut2])
+    fit_s = time.perf_counter() - t0
+    kc = SequenceClassifier(n_neighbors=K).fit(seqs[:cut2], y[:cut2])
+    r.update(labelled_clips=len(seqs), labelled_train=cut2, labelled_fit_wall_s=fit_s,
+             labelled_template_lengths=tc.template_lengths_.tolist(),
+             labelled_inertia_per_iteration=tc.inertia_.sum(axis=1).tolist(),
+             accuracy_dtw_template=float(np.mean(tc.predict(seqs[cut2:]) == y[cut2:])),
+             accuracy_dtw_knn=float(np.mean(kc.predict(seqs[cut2:]) == y[cut2:])))
+    print(json.dumps(r), flush=True)
+    return r
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "dtw_bench.json"))
+    ap.add_argument("--template-out", default=os.path.join(REPO, "profiles", "dtw_template_bench.json"))
     ap.add_argument("--clips", type=int, default=10000)
     ap.add_argument("--replays", type=int, default=5)
     ap.add_argument("--sample", type=int, default=100)
+    ap.add_argument("--legs", default="knn", help="knn: the two k-NN legs (--out); template: the unconstrained "
+                    "k-NN leg and the DBA template leg beside it (--template-out)")
+    ap.add_argument("--n-iter", type=int, default=10)
+    ap.add_argument("--labelled-clips", type=int, default=2000)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("dtw_bench needs the MI355X: nothing is measured without it")
     dev = torch.device("cuda", 0)
     x, lens, cut = sequences(args.clips, dev)
-    res = dict(device=torch.cuda.get_device_name(0), clips=int(x.shape[0]), fp64_vector_peak_datasheet=FP64_VECTOR_PEAK,
-               legs=[leg(x, lens, cut, w, args.replays, args.sample) for w in (None, 10)])
-    with open(args.out, "w") as f:
+    res = dict(device=torch.cuda.get_device_name(0), clips=int(x.shape[0]), fp64_vector_peak_datasheet=FP64_VECTOR_PEAK)
+    if args.legs == "template":
+        knn = leg(x, lens, cut, None, args.replays, args.sample)
+        res["legs"] = [knn, template_leg(x, lens, cut, knn, args.replays, args.n_iter, args.labelled_clips)]
+        out = args.template_out
+    else:
+        res["legs"] = [leg(x, lens, cut, w, args.replays, args.sample) for w in (None, 10)]
+        out = args.out
+    with open(out, "w") as f:
         json.dump(res, f, indent=1)
         f.write("\n")
     print(json.dumps(res))
