@@ -103,7 +103,8 @@ int pick_nsplit_mfma(int64_t Nr, int64_t Nq, int qpb, int cus, double warm = 163
 
 int pick_nsplit(int64_t Nr, int64_t Nq, int qpb)
 {
-    const int64_t qblocks = (Nq + qpb - 1) / qpb;
+    // (an empty query batch is sized like one block: dsp_knn_workspace_bytes takes Nq = 0)
+    const int64_t qblocks = std::max<int64_t>(1, (Nq + qpb - 1) / qpb);
     // Enough workgroups to fill the chip (two per CU), as few reference splits as that allows:
     // a longer split makes a screened distance that enters its top list rarer (~KC / rows seen),
     // and a wave pays for an insertion whenever any of its 64 lanes makes one
@@ -196,7 +197,7 @@ KnnLayout knn_layout(int64_t Nr, int64_t Nq, int D, int k)
     l.pilot_d = l.seed = 0;
     if (l.rstride) {
         // pilot splits: enough workgroups to fill the chip twice over, >= one tile of rows each
-        const int64_t qblocks = (Nq + dsp::mq_qpb(l.KC) - 1) / dsp::mq_qpb(l.KC);
+        const int64_t qblocks = std::max<int64_t>(1, (Nq + dsp::mq_qpb(l.KC) - 1) / dsp::mq_qpb(l.KC));
         l.nsplit_p = (int)std::max<int64_t>(1, std::min<int64_t>({(2 * device_cus() + qblocks - 1) / qblocks,
                                                                   (l.nsample + dsp::MQ_TR - 1) / dsp::MQ_TR, 64}));
         l.pilot_d = o; o += al((size_t)l.nsplit_p * Nq * dsp::PIL_CLS * 4);
@@ -216,6 +217,26 @@ KnnLayout knn_layout(int64_t Nr, int64_t Nq, int D, int k)
 //    at DP = 16; at DP = 32 (8 blocks) 84u = 5.0e-6 < ea = 8e-6 (u = 2^-24);
 //  * D > 32, direct form: D sequential FMAs of non-negative terms, each (q - r) rounded once:
 //    relative (D + 3) u on the sum, plus 4 u (|q|^2 + |r|^2) from the inputs (u = 2^-24); 2x margin.
+//
+// Overflow guard.  These bounds are about finite fp32 numbers.  A screened distance that overflowed
+// is +inf, or NaN in the expanded form (inf - inf, inf * 0 on a padding column); every screen drops
+// such a row (`d < threshold` is false) without filling its list, so the merge would read "list not
+// full: every row is in it" and certify an answer that lacks the row.  So the merge certifies a
+// query only while S = |q|^2 + max |r|^2 < KNN_F32_SAFE = 2^125 (knn_internal.h; |q|^2 in fp64,
+// max |r|^2 the fp32 norm from knn_convert, which is +inf as soon as a component or the norm
+// overflowed), and sends it to the exhaustive fp64 scan otherwise.  Below that threshold nothing
+// overflows, in either form and for every row r of the set:
+//  * a converted component is at most sqrt(S), the expanded form's -2 r_c at most 2 sqrt(S), its
+//    |r|^2 column at most S;
+//  * direct form: (q_c - r_c)^2 <= 2 (q_c^2 + r_c^2), so every term and every partial sum is <= 2 S;
+//  * expanded form: |q_c (-2 r_c)| <= q_c^2 + r_c^2, so |q|^2 plus any subset of the products, in
+//    any order (inside an MFMA block too), plus |r|^2 is within +-(|q|^2 + S + |r|^2) <= 2 S;
+//  * the roundings of the fp32 inputs, of the norms (a chain of <= 4096 FMAs) and of the partial
+//    sums move each of these by a factor below 1 + 1e-3.
+// 2 S (1 + 1e-3) < 2^126.01 against FLT_MAX ~ 2^128: a factor of almost 4 to spare.  The pilot
+// and its seeds use the same arithmetic, so the same holds for them.  The guard is one fp64 add and
+// compare per query on values the merge already holds.  It is about range only: NaN or infinite
+// INPUTS are outside the contract (include/dsp_audiorec.h).
 void knn_err_coeffs(const KnnLayout &l, int D, double &er, double &ea)
 {
     if (!l.hd) {
@@ -265,9 +286,10 @@ extern "C" int dsp_knn_classify(const double *ref, const int32_t *ref_labels, in
     int *fbl = (int *)(ws + l.misc + 16 + 4 * dsp::FB_C);
     float *seedp = l.rstride ? (float *)(ws + l.seed) : nullptr;
     if (hipMemsetAsync(ws + l.misc, 0, 16 + 4 * dsp::FB_C, s) != hipSuccess) return DSP_ERR_HIP;
-    if (Nr > 0 && !(flags & DSP_KNN_REF_READY)) {  // (fit: the reference set in fp32 + its max norm)
+    if (!(flags & DSP_KNN_REF_READY)) {  // (fit: the reference set in fp32 + its max norm)
+        // an empty set too: the merge reads the max norm for its bound and its overflow guard
         if (hipMemsetAsync(mx, 0, 4, s) != hipSuccess) return DSP_ERR_HIP;
-        dsp::launch_knn_convert(s, ref, Nr, D, l.DP, l.exp ? 1 : 0, ref32, mx);
+        if (Nr > 0) dsp::launch_knn_convert(s, ref, Nr, D, l.DP, l.exp ? 1 : 0, ref32, mx);
     }
     dsp::launch_knn_convert(s, query, Nq, D, l.DP, l.exp ? 2 : 0, q32, nullptr);
     if (l.hd) {

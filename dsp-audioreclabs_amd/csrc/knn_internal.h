@@ -41,6 +41,9 @@ static constexpr int PIL_CLS = 32;  // the pilot's row classes (minima) per quer
 #endif
 static constexpr int MG = KNN_MG;  // lanes per query in knn_merge (a power of two <= 64)
 static constexpr int KMAX = 32;    // largest k
+// a query is certified only while |q|^2 + max |r|^2 < 2^125: no fp32 value of any screen then
+// overflows (knn.hip, after knn_err_coeffs)
+static constexpr double KNN_F32_SAFE = 0x1p125;  // 4.25e37; FLT_MAX is just under 2^128
 
 // fallback
 static constexpr int FB_T = 256;

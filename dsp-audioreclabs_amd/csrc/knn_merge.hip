@@ -161,7 +161,11 @@ __device__ __forceinline__ void certify_and_write(int64_t q, int k, float cut, c
                                                   int *fb_count, int *fb_list)
 {
     const double tol = err((double)cut);
-    const bool ok = !(cut < INFINITY) || ((double)cut - tol > kth_of<KM>(dl, k));
+    // fp32 range first (knn.hip, next to knn_err_coeffs): past it a screened distance may have been
+    // +inf or NaN, which no screen keeps and no list counts, so neither "the lists are not full"
+    // nor cut says anything about the rows left out.  (A NaN sum fails the compare as well.)
+    const bool in_range = err.qn + err.rmax < KNN_F32_SAFE;
+    const bool ok = in_range && (!(cut < INFINITY) || ((double)cut - tol > kth_of<KM>(dl, k)));
     if (!ok) {
         const int slot = atomicAdd(fb_count, 1);
         fb_list[slot] = (int)q;

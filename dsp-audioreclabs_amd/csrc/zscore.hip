@@ -1,4 +1,6 @@
-// zscore.hip -- z-score (src/feature_extraction.py:157-181), numpy axis-0 order, for gfx950.
+// zscore.hip -- z-score (src/feature_extraction.py:157-181), numpy axis-0 order, for gfx950:
+// D >= 2 columns sequential over the rows (zscore_fit_kernel), D = 1 numpy's pairwise sum of the
+// one contiguous column (zscore_fit1_kernel).  C-contiguous rows; bit for bit np.mean / np.std.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -7,7 +9,7 @@
 namespace dsp {
 
 #pragma clang fp contract(off)
-// numpy's axis-0 sums are sequential in row order per column, so each column is one dependent
+// D >= 2: numpy's axis-0 sums are sequential in row order per column, so each column is one dependent
 // chain of fp64 adds; the kernel's job is to keep that chain fed.  One workgroup per ZS_C columns:
 // waves 1-3 stage the next ZS_R-row tile of those columns in LDS (coalesced when the row is
 // narrower than ZS_C) while lane c of wave 0 adds the current tile's column c in row order from
@@ -89,6 +91,118 @@ __global__ __launch_bounds__(ZS_T) void zscore_fit_kernel(const double *X, int64
     }
 }
 
+// D = 1.  numpy coalesces the two axes of a C-contiguous (N, 1) array, so its axis-0 reduction is
+// the reduction of one contiguous run, which numpy sums in chunks of 8192 elements (its buffer),
+// the chunks' sums added to the total in order, and each chunk pairwise, not in row order:
+//   sum(a, n) = a[0] + ... + a[n-1] in order                                   for n < 8,
+//             = ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)), then the n % 8 tail in order,
+//               r_j the running sum of a[j], a[j + 8], ...                      for n <= 128,
+//             = sum(a, h) + sum(a + h, n - h), h = n / 2 rounded down to a multiple of 8, otherwise.
+// The std applies the same sum to (x - mean)^2.  This shape is no hot path (the recogniser has 15
+// columns), so the kernel is built to be right: one workgroup; thread 0 walks the chunks and each
+// chunk's recursion with an explicit stack and hands out its next ZS1_T leaf blocks (n <= 128),
+// one thread sums each block, and thread 0 folds the block sums in numpy's order on a value stack
+// -- after a block, one addition for every split, and every chunk, that this block completes.
+static constexpr int ZS1_T = 256, ZS1_CHUNK = 8192, ZS1_STACK = 32;  // two entries per level, 7 levels
+__device__ __forceinline__ double zs1_term(const double *X, int64_t i, int pass, double m)
+{
+    const double v = X[i];
+    if (pass == 0) return v;
+    const double x = v - m;
+    return x * x;
+}
+__device__ __forceinline__ double zs1_block(const double *X, int64_t off, int n, int pass, double m)
+{
+    double res = 0.0;
+    if (n < 8) {
+        for (int i = 0; i < n; i++) res = res + zs1_term(X, off + i, pass, m);
+        return res;
+    }
+    double r[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) r[j] = zs1_term(X, off + j, pass, m);
+    int i = 8;
+    for (; i < n - (n % 8); i += 8)
+#pragma unroll
+        for (int j = 0; j < 8; j++) r[j] = r[j] + zs1_term(X, off + i + j, pass, m);
+    res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+    for (; i < n; i++) res = res + zs1_term(X, off + i, pass, m);
+    return res;
+}
+__global__ __launch_bounds__(ZS1_T) void zscore_fit1_kernel(const double *X, int64_t N, double *mean, double *std)
+{
+    __shared__ int64_t node_off[ZS1_STACK], node_n[ZS1_STACK];  // pending subtrees; n < 0: "add the two on top"
+    __shared__ double vstack[ZS1_STACK];
+    __shared__ int64_t blk_off[ZS1_T];
+    __shared__ int blk_n[ZS1_T], blk_adds[ZS1_T];
+    __shared__ double blk_sum[ZS1_T];
+    __shared__ int nblk_s;
+    __shared__ double m_s;
+    const int tid = threadIdx.x;
+    double m = 0.0;
+    for (int pass = 0; pass < 2; pass++) {
+        int sp = 0, vsp = 1;  // thread 0's stack pointers; vstack[0] is the running total
+        int64_t next = 0;     // the first row of the next chunk
+        if (tid == 0) vstack[0] = 0.0;
+        for (;;) {
+            if (tid == 0) {
+                // the next blocks in order; a batch never ends in front of a pending addition
+                int nb = 0;
+                while (sp > 0 ? (nb < ZS1_T || node_n[sp - 1] < 0) : (nb < ZS1_T && next < N)) {
+                    if (sp == 0) {  // a new chunk: its sum, then total + sum
+                        node_n[sp++] = -1;
+                        node_off[sp] = next;
+                        node_n[sp++] = min((int64_t)ZS1_CHUNK, N - next);
+                        next += ZS1_CHUNK;
+                    }
+                    sp--;
+                    const int64_t off = node_off[sp], n = node_n[sp];
+                    if (n < 0) {
+                        blk_adds[nb - 1]++;
+                    } else if (n <= 128) {
+                        blk_off[nb] = off;
+                        blk_n[nb] = (int)n;
+                        blk_adds[nb] = 0;
+                        nb++;
+                    } else {
+                        int64_t h = n / 2;
+                        h -= h % 8;
+                        node_n[sp++] = -1;
+                        node_off[sp] = off + h;
+                        node_n[sp++] = n - h;
+                        node_off[sp] = off;
+                        node_n[sp++] = h;
+                    }
+                }
+                nblk_s = nb;
+            }
+            __syncthreads();
+            const int nb = nblk_s;
+            if (nb == 0) break;  // the whole workgroup: the recursion is done
+            if (tid < nb) blk_sum[tid] = zs1_block(X, blk_off[tid], blk_n[tid], pass, m);
+            __syncthreads();
+            if (tid == 0)
+                for (int i = 0; i < nb; i++) {
+                    vstack[vsp++] = blk_sum[i];
+                    for (int a = 0; a < blk_adds[i]; a++) {
+                        const double hi = vstack[--vsp], lo = vstack[--vsp];
+                        vstack[vsp++] = lo + hi;
+                    }
+                }
+        }
+        if (pass == 0) {
+            if (tid == 0) m_s = vstack[0] / (double)N;
+            __syncthreads();
+            m = m_s;
+        }
+    }
+    if (tid == 0) {
+        const double sd = sqrt(vstack[0] / (double)N);
+        mean[0] = m;
+        std[0] = sd == 0.0 ? 1.0 : sd;
+    }
+}
+
 __global__ void zscore_apply_kernel(const double *X, int64_t N, int D, const double *mean,
                                     const double *std, double *out)
 {
@@ -105,8 +219,11 @@ extern "C" int dsp_zscore_fit(const double *X, int64_t N, int D, double *mean, d
                               void *stream)
 {
     if (!X || !mean || !std || N < 1 || D < 1) return DSP_ERR_ARGS;
-    hipLaunchKernelGGL(dsp::zscore_fit_kernel, dim3((unsigned)((D + dsp::ZS_C - 1) / dsp::ZS_C)), dim3(dsp::ZS_T), 0,
-                       (hipStream_t)stream, X, N, D, mean, std);
+    if (D == 1)  // one column: numpy's pairwise order (zscore_fit1_kernel)
+        hipLaunchKernelGGL(dsp::zscore_fit1_kernel, dim3(1), dim3(dsp::ZS1_T), 0, (hipStream_t)stream, X, N, mean, std);
+    else
+        hipLaunchKernelGGL(dsp::zscore_fit_kernel, dim3((unsigned)((D + dsp::ZS_C - 1) / dsp::ZS_C)), dim3(dsp::ZS_T),
+                           0, (hipStream_t)stream, X, N, D, mean, std);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? DSP_OK : DSP_ERR_HIP + (int)e;
 }

@@ -224,6 +224,8 @@ class KnnIndex:
         idx = torch.empty((Nq, k), dtype=torch.int32, device=d)
         dist = torch.empty((Nq, k), dtype=torch.float64, device=d)
         pred = torch.empty(Nq, dtype=torch.int32, device=d) if self.labels is not None else None
+        if pred is not None and self.Nr == 0:
+            pred.fill_(-1)  # an empty label array is a null pointer, which skips the vote: no candidate, no label
         flags = _hip.KNN_REF_READY if self._ready else 0
         rc = _hip.lib().dsp_knn_classify(_hip.ptr(self.ref), _hip.ptr(self.labels), self.Nr, _hip.ptr(q), Nq,
                                          self.D, k, int(self_offset), self.n_classes, _hip.ptr(idx),
@@ -242,9 +244,13 @@ def knn_classify(ref, ref_labels, query, k, self_offset=-1, n_classes=None, with
     prepared reference set across queries).
 
     ref [Nr, D] / query [Nq, D] float64 (cast if needed), ref_labels int [Nr].
-    Returns (idx int32 [Nq,k], dist float64 [Nq,k], pred int32 [Nq] or None).  A dict passed as
-    ``stats`` receives "fallbacks": the queries answered by the exhaustive fp64 fallback (one host
-    sync).
+    Returns (idx int32 [Nq,k], dist float64 [Nq,k], pred int32 [Nq] or None).  Where a query has
+    fewer than k candidates idx is -1 and dist inf; with no candidate at all pred is -1.  A dict
+    passed as ``stats`` receives "fallbacks": the queries answered by the exhaustive fp64 fallback
+    (one host sync).
+
+    The values must be finite (NaN and infinity are outside the contract, as for scikit-learn, and
+    are not checked); any finite magnitude whose float64 squared distances are finite is exact.
     """
     return KnnIndex(ref, ref_labels, k, n_classes, with_pred).query(query, self_offset, stats)
 
@@ -655,7 +661,11 @@ class TreeIndex:
 
 
 def zscore_fit(X):
-    """normalize_features' mean/std (src/feature_extraction.py:171-177) on the device."""
+    """normalize_features' mean/std (src/feature_extraction.py:171-177) on the device: bit for bit
+    ``np.mean(X, axis=0)`` and ``np.std(X, axis=0)`` (0 -> 1) of a C-contiguous float64 [N, D] array,
+    one column (numpy's pairwise order) included.  Any other layout is made C-contiguous first --
+    the reference's callers build C-ordered arrays -- so a Fortran-ordered X gets the C-ordered
+    array's sums, which numpy's own sums over that layout need not equal."""
     import torch
     d = _hip.require_device()
     X = _as_device(X, torch.float64, d)

@@ -172,12 +172,20 @@ int dsp_extract_general(const void *pcm, int sample_bytes, const int64_t *offset
  * re-solved exhaustively in fp64 on the device.  Exact-distance ties are ordered by smaller
  * reference index.
  *
+ * Inputs must be finite: NaN or infinite components are outside the contract (scikit-learn
+ * refuses them) and are not looked for.  Any finite magnitude whose fp64 squared distances are
+ * finite is inside it: a query whose fp32 screen could have overflowed (|q|^2 + max |r|^2 not
+ * below 2^125, knn.hip next to knn_err_coeffs) is not certified and goes to the exhaustive fp64
+ * scan, and one whose screen underflowed fails the ordinary certification and goes there too.
+ *
  * ref        float64 [Nr, D] row-major,  ref_labels int32 [Nr] in [0, n_classes)
  * query      float64 [Nq, D] row-major
  * self_offset  >= 0: query q is reference row self_offset + q and is excluded from its own
  *              neighbour list (kneighbors(X=None) semantics); -1: no exclusion.
- * idx        int32 [Nq, k] (-1 where fewer than k candidates), dist float64 [Nq, k],
- * pred       int32 [Nq] (may be NULL, or ref_labels NULL, to skip the vote)
+ * idx        int32 [Nq, k] (-1 where fewer than k candidates), dist float64 [Nq, k] (+inf there),
+ * pred       int32 [Nq] (may be NULL, or ref_labels NULL, to skip the vote: pred is then left
+ *            untouched).  The vote is over the candidates there are; a query with no candidate
+ *            at all (Nr = 0, or Nr = 1 and that row is the query's own) has no label: pred = -1.
  * workspace  device scratch of dsp_knn_workspace_bytes(Nr, Nq, D, k) bytes.  Its first part holds
  *            the reference set converted for the screen, at offsets that depend on (Nr, D) only.
  * flags      DSP_KNN_REF_READY: the workspace already holds that conversion, left by an earlier call
@@ -198,9 +206,16 @@ int dsp_knn_classify(const double *ref, const int32_t *ref_labels, int64_t Nr, c
 
 /*
  * normalize_features (src/feature_extraction.py:157-181): column mean and population std
- * (ddof = 0, numpy axis-0 order: sequential over rows), std == 0 -> 1, then (X - mean) / std.
+ * (ddof = 0), std == 0 -> 1, then (X - mean) / std, bit for bit np.mean / np.std over axis 0 of
+ * a C-contiguous [N, D] array.  That is numpy's summation order, which depends on D:
+ *   D >= 2  each column sequentially over the rows;
+ *   D == 1  numpy coalesces the axes and sums the one contiguous column in chunks of 8192 rows
+ *           (its buffer), adding the chunks' sums in order, and each chunk of n rows pairwise: in
+ *           order for n < 8; for n <= 128 eight running sums over strides of 8 combined as
+ *           ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), then the n % 8 tail in order; otherwise split at
+ *           n / 2 rounded down to a multiple of 8, recursively.  The std sums (x - mean)^2 alike.
  * dsp_zscore_fit writes mean/std [D] (std already with the 0 -> 1 substitution);
- * dsp_zscore_apply writes out [N, D] (may alias X).  float64 throughout.
+ * dsp_zscore_apply writes out [N, D] (may alias X).  float64 throughout, X row-major.
  */
 int dsp_zscore_fit(const double *X, int64_t N, int D, double *mean, double *std, void *stream);
 int dsp_zscore_apply(const double *X, int64_t N, int D, const double *mean, const double *std,

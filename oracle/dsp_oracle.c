@@ -19,7 +19,8 @@
  *    (8 interleaved accumulators for n <= 128, recursive halving at
  *    multiples of 8 above, plain loop for n < 8).
  *  - np.mean/np.std along axis 0 of a C-contiguous 2-D array are plain
- *    sequential row sums.
+ *    sequential row sums -- except with ONE column, where numpy coalesces
+ *    the axes and sums the contiguous column like a 1-D array (above).
  *  - np.percentile(q=90, method='linear'): virtual index (n-1)*0.9, numpy's
  *    _lerp (b - d*(1-g) when g >= 0.5, a + d*g otherwise).
  *  - sklearn KDTree euclidean distances: sequential d += t*t, no FMA, sqrt.
@@ -473,6 +474,20 @@ int ora_process_batch_i16(const int16_t *pcm, const int64_t *offsets, int64_t B,
 /* ------------------------------------------------------------------------ */
 void ora_zscore_fit(const double *X, int64_t n, int d, double *mean, double *std)
 {
+    if (d == 1) {
+        /* One column: numpy coalesces the axes of a C-contiguous (n, 1) array, so the axis-0
+         * reduction is that of one contiguous run: ora_np_sum (8192-element chunks added in
+         * order, each summed pairwise), for the mean and for the sum of (x - mean)^2 alike. */
+        double *t = (double *)malloc(sizeof(double) * (size_t)(n > 0 ? n : 1));
+        mean[0] = ora_np_sum(X, n) / (double)n;
+        for (int64_t i = 0; i < n; i++) {
+            double x = X[i] - mean[0];
+            t[i] = x * x;
+        }
+        std[0] = sqrt(ora_np_sum(t, n) / (double)n);
+        free(t);
+        return;
+    }
     for (int c = 0; c < d; c++) mean[c] = 0.0;
     for (int64_t i = 0; i < n; i++)
         for (int c = 0; c < d; c++) mean[c] += X[i * d + c];
@@ -538,7 +553,7 @@ void ora_knn(const double *ref, const int32_t *ref_lbl, int64_t Nr, const double
             int bl = 0;
             for (int c = 1; c < n_classes; c++)
                 if (cnt[c] > cnt[bl]) bl = c; /* scipy.stats.mode: smallest label wins ties */
-            pred[qi] = bl;
+            pred[qi] = nb > 0 ? bl : -1; /* no candidate at all: no label */
         }
     }
     free(best);
