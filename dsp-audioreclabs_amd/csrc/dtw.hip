@@ -16,29 +16,11 @@
 //
 // Three kernels:
 //   dtw_dp<F>  one wave per tile of 64 reference sequences against ONE query (a workgroup is one
-//              wave).  Lane l owns the pair (query, reference l); the query's frames are the same
-//              for every lane, so they are read with wave-uniform addresses (scalar loads, no LDS
-//              and no vector-memory traffic per cell), and only the lane's own reference frame --
-//              F values per DP row -- comes through the vector path, prefetched one row ahead.
-//              The lane keeps a strip of 32 DP cells (32 consecutive query frames) in registers and
-//              sweeps its reference's frames in the outer loop, the strip loop fully unrolled so
-//              the register array is never indexed at run time.  Strips are END-aligned (the last
-//              one ends at query frame n - 1, the first may start before frame 0 with those cells
-//              held at +inf), so the strip's last register is both the edge handed to the next
-//              strip and, in the last strip, the result; dtw_pad first copies the chunk's queries
-//              behind 32 frames of zeros, so those reads stay inside the copy's row and every
-//              strip reads its 32 query frames at constant offsets from one base.  A strip hands
-//              its edge column D(., last) to the next one through a per-wave array in the
-//              workspace laid out [row][lane] (coalesced); the first strip reads +inf, the last
-//              writes nothing.
-//              Loop bounds are wave-uniform (the largest reference length and band of the wave's
-//              lanes); rows past a lane's own length compute values nothing reads.  Rows of a strip
-//              that are admissible for no lane are skipped; a row that is admissible in all its 32
-//              cells for every lane runs a body without the band select (row 0, with the start
-//              cell, has a body of its own).  Waves are persistent: a launch has at most
-//              DTW_WAVES of them, each walking tiles wave, wave + G, ... so the edge arrays are
-//              bounded.
-//   dtw_pad    the padded copy of a chunk of queries (above).
+//              wave): dtw_internal.h's sweep with the query as the uniform side and a lane per
+//              reference.  Waves are persistent: a launch has at most DTW_WAVES of them, each
+//              walking tiles wave, wave + G, ... so the edge arrays are bounded.
+//   dtw_pad    the padded copy of a chunk of uniform-side sequences that the sweep reads (also
+//              dtw_align.hip's, through dtw_launch_pad).
 //   dtw_topk   one wave per query over that query's distance row: k rounds of "the smallest
 //              (distance, index) pair after the last one taken", a butterfly minimum per round.
 //              Negligible next to the DP.  The vote is dsp_knn_classify's: uniform, the smallest
@@ -49,7 +31,7 @@
 #include <algorithm>
 
 #include "dsp_audiorec.h"
-#include "dtw_internal.h"  // the plan's constants, wave_max_uniform, dtw_min (shared with dtw_align.hip)
+#include "dtw_internal.h"  // the plan, the row body and the sweep (shared with dtw_align.hip)
 
 namespace dsp {
 
@@ -57,41 +39,6 @@ static constexpr int DTW_KMAX = 32;                   // largest k
 static constexpr size_t DTW_EDGE_CAP = 256u << 20;    // bytes of edge arrays per launch
 static constexpr size_t DTW_CHUNK_CAP = 64u << 20;    // bytes of distance rows per query chunk
 static constexpr int DTW_QCHUNK = 1024;               // queries per chunk at most
-
-#pragma clang fp contract(off)
-// One DP row of a strip: cells (r, c0 .. c0 + 31).  prev holds the row above and is replaced by this
-// row; diag = D(r-1, c0-1), left = D(r, c0-1).  qs: the padded query's frame c0 (wave-uniform; the
-// frames before frame 0 are zeros, so their cells' costs are finite and the cells stay +inf like
-// their neighbours).  MODE 0: every cell of the row is admissible for every lane; 1: the band select
-// (three more instructions per cell); 2: row 0, the band select and the start cell.
-template <int F, int MODE>
-__device__ __forceinline__ void dtw_row(double (&prev)[DTW_STRIP], double diag, double left, const double (&bf)[F],
-                                        const double *__restrict__ qs, int c0, int r, int w)
-{
-#pragma unroll
-    for (int j = 0; j < DTW_STRIP; j++) {
-        const int c = c0 + j;
-        const double *qc = qs + j * F;
-        double t = bf[0] - qc[0];
-        double cost = t * t;
-#pragma unroll
-        for (int f = 1; f < F; f++) {
-            t = bf[f] - qc[f];
-            cost = cost + t * t;
-        }
-        double best = dtw_min(dtw_min(prev[j], left), diag);
-        if (MODE == 2 && c == 0) best = 0.0;  // D(0,0) = c(0,0)
-        double v = cost + best;
-        if (MODE != 0) {
-            const int d = r - c;
-            v = (d < 0 ? -d : d) <= w ? v : (double)INFINITY;
-        }
-        diag = prev[j];
-        prev[j] = v;
-        left = v;
-    }
-}
-#pragma clang fp contract(on)
 
 // apad [Nq, Tq + DTW_STRIP, F]: DTW_STRIP frames of zeros, then a's row -- the first strip of an
 // end-aligned walk starts up to 31 frames before frame 0, and reads them here instead of outside the row
@@ -103,6 +50,12 @@ __global__ __launch_bounds__(256) void dtw_pad(const double *__restrict__ a, int
         const int64_t q = i / rowp, e = i - q * rowp - (int64_t)DTW_STRIP * F;
         apad[i] = e < 0 ? 0.0 : a[q * Tq * F + e];
     }
+}
+void dtw_launch_pad(hipStream_t s, const double *in, int64_t rows, int T, int F, double *out)
+{
+    const int64_t elems = rows * (T + DTW_STRIP) * F;
+    hipLaunchKernelGGL(dtw_pad, dim3((unsigned)std::min<int64_t>((elems + 255) / 256, 4096)), dim3(256), 0, s, in, rows,
+                       T, F, out);
 }
 
 // apad: the uniform side (one sequence per tile, padded by dtw_pad), b: the lanes' side.  dist [Nq, Nr].
@@ -124,56 +77,9 @@ __global__ __launch_bounds__(64) void dtw_dp(const double *__restrict__ apad, co
         if (m < 1 || m > Tr) m = 0;
         double res = INFINITY;
         const int mmax = wave_max_uniform(m);
-        if (n >= 1 && n <= Tq && mmax > 0) {
-            const double *__restrict__ q = apad + (uq * (Tq + DTW_STRIP) + DTW_STRIP) * F;  // frame 0
-            const double *__restrict__ br = b + (inr ? ref : 0) * (int64_t)Tr * F;
-            const int dl = n > m ? n - m : m - n;
-            const int w = window < 0 ? DTW_WBIG : min(max(window, dl), DTW_WBIG);
-            const int wmax = wave_max_uniform(m > 0 ? w : 0);
-            const int wmin = -wave_max_uniform(m > 0 ? -w : -DTW_WBIG);
-            const int S = (n + DTW_STRIP - 1) / DTW_STRIP;
-            for (int s = 0; s < S; s++) {
-                const int c0 = n - DTW_STRIP * (S - s);  // end-aligned: c0 < 0 only in strip 0
-                const int cf = max(c0, 0);
-                const int rlo = max(0, cf - wmax), rhi = min(mmax, c0 + DTW_STRIP + wmax);
-                if (rlo >= rhi) continue;
-                const bool has_left = s > 0, has_right = s < S - 1;
-                const double *__restrict__ qs = q + c0 * F;
-                double prev[DTW_STRIP];
-#pragma unroll
-                for (int j = 0; j < DTW_STRIP; j++) prev[j] = INFINITY;
-                auto left_of = [&](int r) {  // D(r, c0 - 1) from the strip before, +inf outside the band
-                    const int d = r - (c0 - 1);
-                    return (has_left && (d < 0 ? -d : d) <= w) ? edge[(size_t)r * 64] : (double)INFINITY;
-                };
-                double dg = rlo > 0 ? left_of(rlo - 1) : (double)INFINITY;
-                double bf[F], left = left_of(rlo);
-#pragma unroll
-                for (int f = 0; f < F; f++) bf[f] = br[(size_t)rlo * F + f];
-                for (int r = rlo; r < rhi; r++) {
-                    const int rn = min(r + 1, rhi - 1);  // the next row's loads, issued before this row's cells
-                    double bfn[F];
-#pragma unroll
-                    for (int f = 0; f < F; f++) bfn[f] = br[(size_t)rn * F + f];
-                    const double leftn = left_of(rn);
-                    const bool full = r > 0 && r - cf <= wmin && c0 + DTW_STRIP - 1 - r <= wmin;
-                    if (r == 0)
-                        dtw_row<F, 2>(prev, dg, left, bf, qs, c0, r, w);
-                    else if (full)
-                        dtw_row<F, 0>(prev, dg, left, bf, qs, c0, r, w);
-                    else
-                        dtw_row<F, 1>(prev, dg, left, bf, qs, c0, r, w);
-                    dg = left;
-                    if (has_right)
-                        edge[(size_t)r * 64] = prev[DTW_STRIP - 1];
-                    else if (r == m - 1)
-                        res = prev[DTW_STRIP - 1];
-                    left = leftn;
-#pragma unroll
-                    for (int f = 0; f < F; f++) bf[f] = bfn[f];
-                }
-            }
-        }
+        if (n >= 1 && n <= Tq && mmax > 0)
+            res = dtw_sweep<F, false>(apad + (uq * (Tq + DTW_STRIP) + DTW_STRIP) * F,  // frame 0
+                                      b + (inr ? ref : 0) * (int64_t)Tr * F, n, m, mmax, window, Tr, edge, nullptr);
         if (inr) dist[uq * Nr + ref] = res < INFINITY ? sqrt(res) : (double)INFINITY;
     }
 }
@@ -248,8 +154,7 @@ __global__ __launch_bounds__(64) void dtw_topk(const double *__restrict__ rows, 
 // ---- host side ----
 static bool dtw_in_plan(int64_t Nr, int64_t Nq, int Tr, int Tq, int F)
 {
-    return Nr >= 0 && Nr <= 0x7fffffff && Nq >= 0 && Tr >= 1 && Tr <= DTW_TMAX && Tq >= 1 && Tq <= DTW_TMAX &&
-           F >= 1 && F <= DTW_FMAX;
+    return Nr >= 0 && Nr <= 0x7fffffff && Nq >= 0 && dtw_shape_in_plan(Tr, Tq, F);
 }
 // waves of a launch over nq queries, and the bytes of their edge arrays
 static int dtw_waves(int64_t nq, int64_t Nr, int Tr)
@@ -261,12 +166,7 @@ static int dtw_waves(int64_t nq, int64_t Nr, int Tr)
 static size_t dtw_edge_bytes(int64_t nq, int64_t Nr, int Tr, int Tq)
 {
     if (Tq <= DTW_STRIP) return 256;  // one strip: no edge is ever read or written
-    return ((size_t)dtw_waves(nq, Nr, Tr) * Tr * 64 * 8 + 255) & ~(size_t)255;
-}
-// the padded copy of one chunk's queries
-static size_t dtw_pad_bytes(int64_t nq, int Tq, int F)
-{
-    return (((size_t)nq * (Tq + DTW_STRIP) * F * 8) + 255) & ~(size_t)255;
+    return up256((size_t)dtw_waves(nq, Nr, Tr) * Tr * 64 * 8);
 }
 static int64_t dtw_chunk(int64_t Nr, int64_t Nq)
 {
@@ -281,19 +181,8 @@ static int dtw_launch_dp(hipStream_t s, const double *a_rows, const int32_t *len
 {
     const int G = dtw_waves(nq, Nr, Tr);
     if (G < 1) return DSP_OK;
-    const int64_t pad_elems = nq * (Tq + DTW_STRIP) * F;
-    hipLaunchKernelGGL(dtw_pad, dim3((unsigned)std::min<int64_t>((pad_elems + 255) / 256, 4096)), dim3(256), 0, s,
-                       a_rows, nq, Tq, F, a);
-    const dim3 grid((unsigned)G), block(64);
-#define DTW_GO(FF)                                                                                                 \
-    case FF:                                                                                                       \
-        hipLaunchKernelGGL(dtw_dp<FF>, grid, block, 0, s, a, len_a, nq, Tq, b, len_b, Nr, Tr, window, dist, edge); \
-        break;
-    switch (F) {
-        DTW_GO(1) DTW_GO(2) DTW_GO(3) DTW_GO(4) DTW_GO(5) DTW_GO(6) DTW_GO(7) DTW_GO(8)
-    default: return DSP_ERR_ARGS;
-    }
-#undef DTW_GO
+    dtw_launch_pad(s, a_rows, nq, Tq, F, a);
+    DTW_LAUNCH_F(F, dtw_dp, dim3((unsigned)G), dim3(64), 0, s, a, len_a, nq, Tq, b, len_b, Nr, Tr, window, dist, edge)
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? DSP_OK : DSP_ERR_HIP + (int)e;
 }

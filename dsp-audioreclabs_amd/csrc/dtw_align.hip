@@ -24,13 +24,12 @@
 // member is copied bit for bit with inertia 0.0.
 //
 // Kernels:
-//   dtw_align_dp<F>  dtw_dp<F>'s shape: one wave per tile of 64 members of ONE group, the group's a
-//              sequence wave-uniform (scalar loads from a copy behind 32 zero frames), a lane per
-//              member, 32 cells of an end-aligned strip in registers, the edge column through a
-//              per-wave [row][lane] array.  Beyond D each cell yields two bits (does D(i-1, j-1),
-//              does D(i-1, j) equal the minimum: the rule's first two candidates); the 2 x 32 bits
-//              of a strip row are one 64-bit word per lane, stored [strip][row][lane] -- one
-//              coalesced 512-byte store per row, nothing per cell.
+//   dtw_align_dp<F>  one wave per tile of 64 members of ONE group: dtw_internal.h's sweep with DIR,
+//              the group's a sequence as the uniform side and a lane per member.  Beyond D each
+//              cell yields two bits (does D(i-1, j-1), does D(i-1, j) equal the minimum: the rule's
+//              first two candidates -- the sweep's diagonal and its "left"); the 2 x 32 bits of a
+//              strip row are one 64-bit word per lane, stored [strip][row][lane] -- one coalesced
+//              512-byte store per row, nothing per cell.
 //              After the tile's strips each lane walks its own path back through those words (at
 //              most n + m - 1 steps; a word is re-read only when the strip or the row changes) and
 //              writes lo / hi.  The walk clamps at i = 0 and j = 0, so it ends and stays inside the
@@ -38,7 +37,6 @@
 //              tiles w, w + G, ... of the launch's groups, counted by walking group_start (scalar
 //              loads, at most 1024 groups per launch), so the words and the edges are per wave and
 //              bounded whatever P is.
-//   dtw_align_pad    the padded copy of a chunk of a.
 //   dba_sums   a thread per (pair, frame, channel): S_k from the pair's ranges, all pairs in parallel.
 //   dba_accumulate / dba_finish   a thread per (template, frame, channel): acc = acc + S_k over the
 //              chunk's pairs in list order, then the division.
@@ -56,62 +54,6 @@ static constexpr size_t DTW_ALIGN_WAVE_CAP = 1024u << 20;  // bytes of code word
 static constexpr size_t DTW_ALIGN_RANGE_CAP = 128u << 20;  // bytes of lo, hi and S_k per DBA pair chunk
 static constexpr int DTW_ALIGN_GCHUNK = 1024;              // groups per launch at most
 static constexpr int DBA_BATCH = 16;                       // members whose loads a DBA thread keeps in flight
-
-#pragma clang fp contract(off)
-// dtw_row (dtw.hip) with the predecessor codes: cells (r, c0 .. c0 + 31) of a strip, r the b frame,
-// c the a frame.  prev holds the row above -- D(i, j-1) -- and is replaced; diag = D(i-1, j-1),
-// left = D(i-1, j).  w0 collects "the diagonal equals the minimum", w1 "the a-step (i-1, j) does", one
-// bit per cell, cell 31 in bit 0: diagonal if w0's bit is set, else a-step if w1's is, else b-step.
-template <int F, int MODE>
-__device__ __forceinline__ void dtw_row_dir(double (&prev)[DTW_STRIP], double diag, double left, const double (&bf)[F],
-                                            const double *__restrict__ qs, int c0, int r, int w, uint32_t &w0,
-                                            uint32_t &w1)
-{
-    uint32_t md = 0, ml = 0;
-#pragma unroll
-    for (int j = 0; j < DTW_STRIP; j++) {
-        const int c = c0 + j;
-        const double *qc = qs + j * F;
-        double t = bf[0] - qc[0];
-        double cost = t * t;
-#pragma unroll
-        for (int f = 1; f < F; f++) {
-            t = bf[f] - qc[f];
-            cost = cost + t * t;
-        }
-        double best = dtw_min(dtw_min(prev[j], left), diag);
-        // m = 2 m + (x == best): each compare's bit is shifted in through the carry, two instructions
-        // per bit (a select and an or of a constant per bit are three)
-        asm("v_cmp_eq_f64 vcc, %2, %4\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc\n\t"
-            "v_cmp_eq_f64 vcc, %3, %4\n\tv_addc_co_u32 %1, vcc, %1, %1, vcc"
-            : "+v"(md), "+v"(ml)
-            : "v"(diag), "v"(left), "v"(best)
-            : "vcc");
-        if (MODE == 2 && c == 0) best = 0.0;  // D(0,0) = c(0,0)
-        double v = cost + best;
-        if (MODE != 0) {
-            const int d = r - c;
-            v = (d < 0 ? -d : d) <= w ? v : (double)INFINITY;
-        }
-        diag = prev[j];
-        prev[j] = v;
-        left = v;
-    }
-    w0 = md;
-    w1 = ml;
-}
-#pragma clang fp contract(on)
-
-// apad [nc, Ta + DTW_STRIP, F]: DTW_STRIP frames of zeros, then a's row (dtw_pad's layout)
-__global__ __launch_bounds__(256) void dtw_align_pad(const double *__restrict__ a, int64_t nc, int Ta, int F,
-                                                     double *__restrict__ apad)
-{
-    const int64_t rowp = (int64_t)(Ta + DTW_STRIP) * F, total = nc * rowp;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int64_t q = i / rowp, e = i - q * rowp - (int64_t)DTW_STRIP * F;
-        apad[i] = e < 0 ? 0.0 : a[q * Ta * F + e];
-    }
-}
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
@@ -155,57 +97,9 @@ __global__ __launch_bounds__(64) void dtw_align_dp(const double *__restrict__ ap
             if (m < 1 || m > Tb) m = 0;
             double res = INFINITY;
             const int mmax = wave_max_uniform(m);
-            if (nok && mmax > 0) {
-                const double *__restrict__ br = b + (int64_t)(rok ? ref : 0) * Tb * F;
-                const int dl = n > m ? n - m : m - n;
-                const int w = window < 0 ? DTW_WBIG : min(max(window, dl), DTW_WBIG);
-                const int wmax = wave_max_uniform(m > 0 ? w : 0);
-                const int wmin = -wave_max_uniform(m > 0 ? -w : -DTW_WBIG);
-                for (int s = 0; s < S; s++) {
-                    const int c0 = n - DTW_STRIP * (S - s);  // end-aligned: c0 < 0 only in strip 0
-                    const int cf = max(c0, 0);
-                    const int rlo = max(0, cf - wmax), rhi = min(mmax, c0 + DTW_STRIP + wmax);
-                    if (rlo >= rhi) continue;
-                    const bool has_left = s > 0, has_right = s < S - 1;
-                    const double *__restrict__ qs = q + c0 * F;
-                    unsigned long long *drow = dir + (size_t)s * (size_t)Tb * 64;
-                    double prev[DTW_STRIP];
-#pragma unroll
-                    for (int j = 0; j < DTW_STRIP; j++) prev[j] = INFINITY;
-                    auto left_of = [&](int r) {  // D(r, c0 - 1) from the strip before, +inf outside the band
-                        const int d = r - (c0 - 1);
-                        return (has_left && (d < 0 ? -d : d) <= w) ? edge[(size_t)r * 64] : (double)INFINITY;
-                    };
-                    double dg = rlo > 0 ? left_of(rlo - 1) : (double)INFINITY;
-                    double bf[F], left = left_of(rlo);
-#pragma unroll
-                    for (int f = 0; f < F; f++) bf[f] = br[(size_t)rlo * F + f];
-                    for (int r = rlo; r < rhi; r++) {
-                        const int rn = min(r + 1, rhi - 1);  // the next row's loads, issued before this row's cells
-                        double bfn[F];
-#pragma unroll
-                        for (int f = 0; f < F; f++) bfn[f] = br[(size_t)rn * F + f];
-                        const double leftn = left_of(rn);
-                        const bool full = r > 0 && r - cf <= wmin && c0 + DTW_STRIP - 1 - r <= wmin;
-                        uint32_t w0, w1;
-                        if (r == 0)
-                            dtw_row_dir<F, 2>(prev, dg, left, bf, qs, c0, r, w, w0, w1);
-                        else if (full)
-                            dtw_row_dir<F, 0>(prev, dg, left, bf, qs, c0, r, w, w0, w1);
-                        else
-                            dtw_row_dir<F, 1>(prev, dg, left, bf, qs, c0, r, w, w0, w1);
-                        dg = left;
-                        if (lo) drow[(size_t)r * 64] = ((unsigned long long)w1 << 32) | w0;
-                        if (has_right)
-                            edge[(size_t)r * 64] = prev[DTW_STRIP - 1];
-                        else if (r == m - 1)
-                            res = prev[DTW_STRIP - 1];
-                        left = leftn;
-#pragma unroll
-                        for (int f = 0; f < F; f++) bf[f] = bfn[f];
-                    }
-                }
-            }
+            if (nok && mmax > 0)
+                res = dtw_sweep<F, true>(q, b + (int64_t)(rok ? ref : 0) * Tb * F, n, m, mmax, window, Tb, edge,
+                                         lo ? dir : nullptr);
             if (!inr) continue;
             if (dist) dist[p] = res < INFINITY ? sqrt(res) : (double)INFINITY;
             if (d2) d2[p - p_lo] = res;
@@ -352,15 +246,12 @@ __global__ __launch_bounds__(256) void dba_finish(const double *__restrict__ tmp
 // ---- host side ----
 static bool align_in_plan(int64_t Na, int64_t Nb, int64_t P, int Ta, int Tb, int F)
 {
-    return Na >= 0 && Na < 0x7fffffff && Nb >= 0 && Nb <= 0x7fffffff && P >= 0 && P <= 0x7fffffff && Ta >= 1 &&
-           Ta <= DTW_TMAX && Tb >= 1 && Tb <= DTW_TMAX && F >= 1 && F <= DTW_FMAX;
+    return Na >= 0 && Na < 0x7fffffff && Nb >= 0 && Nb <= 0x7fffffff && P >= 0 && P <= 0x7fffffff &&
+           dtw_shape_in_plan(Ta, Tb, F);
 }
-static size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-// a wave's code words [strips][Tb][64] and its edge column [Tb][64]
-static size_t align_wave_bytes(int Ta, int Tb)
-{
-    return ((size_t)((Ta + DTW_STRIP - 1) / DTW_STRIP) + 1) * (size_t)Tb * 64 * 8;
-}
+// a wave's code words [strips][Tb][64], and with them its edge column [Tb][64]
+static size_t align_dir_bytes(int Ta, int Tb) { return (size_t)((Ta + DTW_STRIP - 1) / DTW_STRIP) * Tb * 64 * 8; }
+static size_t align_wave_bytes(int Ta, int Tb) { return align_dir_bytes(Ta, Tb) + (size_t)Tb * 64 * 8; }
 // waves of a launch over nc groups and np pairs: no more than its tiles can be
 static int align_waves(int64_t nc, int64_t np, int Ta, int Tb)
 {
@@ -387,7 +278,7 @@ static AlignPlan align_plan(int64_t Na, int64_t P, int Ta, int Tb, int F)
     pl.pc = align_pair_chunk(P, Ta, F);
     pl.G = align_waves(pl.nc, P, Ta, Tb);
     pl.waves = up256((size_t)pl.G * align_wave_bytes(Ta, Tb));
-    pl.pad = up256((size_t)pl.nc * (Ta + DTW_STRIP) * F * 8);
+    pl.pad = dtw_pad_bytes(pl.nc, Ta, F);
     pl.ranges = up256((size_t)pl.pc * Ta * 4);
     pl.sums = up256((size_t)pl.pc * Ta * F * 8);
     pl.d2 = up256((size_t)pl.pc * 8);
@@ -402,26 +293,12 @@ static int align_launch(hipStream_t s, const AlignPlan &pl, void *ws, bool pad, 
                         int64_t p_hi, double *dist, double *d2, int32_t *lo, int32_t *hi)
 {
     unsigned long long *dir = (unsigned long long *)ws;
-    const size_t dir_bytes = (size_t)pl.G * (size_t)((Ta + DTW_STRIP - 1) / DTW_STRIP) * Tb * 64 * 8;
-    double *edge = (double *)((char *)ws + dir_bytes);
+    double *edge = (double *)((char *)ws + (size_t)pl.G * align_dir_bytes(Ta, Tb));
     double *apad = (double *)((char *)ws + pl.waves);
-    if (pad) {
-        const int64_t pad_elems = nc * (Ta + DTW_STRIP) * F;
-        hipLaunchKernelGGL(dtw_align_pad, dim3((unsigned)std::min<int64_t>((pad_elems + 255) / 256, 4096)), dim3(256),
-                           0, s, a + c0 * Ta * F, nc, Ta, F, apad);
-    }
+    if (pad) dtw_launch_pad(s, a + c0 * Ta * F, nc, Ta, F, apad);
     const int G = std::min(pl.G, align_waves(nc, p_hi - p_lo, Ta, Tb));
-    const dim3 grid((unsigned)G), block(64);
-#define DTW_GO(FF)                                                                                                   \
-    case FF:                                                                                                         \
-        hipLaunchKernelGGL(dtw_align_dp<FF>, grid, block, 0, s, apad, len_a + c0, group_start + c0, (int)nc, Ta, b,  \
-                           len_b, Nb, Tb, members, (int)p_lo, (int)p_hi, window, dist, d2, lo, hi, edge, dir);       \
-        break;
-    switch (F) {
-        DTW_GO(1) DTW_GO(2) DTW_GO(3) DTW_GO(4) DTW_GO(5) DTW_GO(6) DTW_GO(7) DTW_GO(8)
-    default: return DSP_ERR_ARGS;
-    }
-#undef DTW_GO
+    DTW_LAUNCH_F(F, dtw_align_dp, dim3((unsigned)G), dim3(64), 0, s, apad, len_a + c0, group_start + c0, (int)nc, Ta, b,
+                 len_b, Nb, Tb, members, (int)p_lo, (int)p_hi, window, dist, d2, lo, hi, edge, dir)
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? DSP_OK : DSP_ERR_HIP + (int)e;
 }
