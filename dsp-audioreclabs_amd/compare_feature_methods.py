@@ -39,7 +39,8 @@ def load_both_methods(data_dir=None, frame_length=None, frame_shift=None, window
     return X_stat, X_seq, y, lengths
 
 
-def compare(data_dir=None, classifiers=None, test_size=0.2, random_state=42, dtw=False, dtw_template=False):
+def compare(data_dir=None, classifiers=None, test_size=0.2, random_state=42, dtw=False, dtw_template=False,
+            hmm=False):
     """:124-214: each classifier on both feature sets, the reference's split and normalisation
     -> {classifier: {'statistical': acc, 'sequence': acc, 'diff': sequence - statistical}}.
     KNN on the flattened sequences (2 x max_frames columns) runs on the device like the 15-d
@@ -48,7 +49,9 @@ def compare(data_dir=None, classifiers=None, test_size=0.2, random_state=42, dtw
     'sequence' the accuracy of k-NN under dynamic time warping (src.models.SequenceClassifier,
     n_neighbors=3) on the UNPADDED (E, ZCR) sequences of the same split.
     dtw_template=True (an extension) adds the row 'DTW-template' beside it: the same, for the nearest
-    of one DBA template per class (src.models.TemplateClassifier, its defaults)."""
+    of one DBA template per class (src.models.TemplateClassifier, its defaults).
+    hmm=True (an extension) adds the row 'HMM' beside them: the same, for one left-to-right Gaussian
+    HMM per class (src.models.HmmClassifier, its defaults)."""
     from sklearn.model_selection import train_test_split
     X_stat, X_seq, y, lengths = load_both_methods(data_dir)
     X_flat = X_seq.reshape(len(X_seq), -1)
@@ -68,7 +71,7 @@ def compare(data_dir=None, classifiers=None, test_size=0.2, random_state=42, dtw
             acc[method] = float(clf.evaluate(te, y_te)['accuracy'])
         results[name] = {'statistical': acc['statistical'], 'sequence': acc['sequence'],
                          'diff': acc['sequence'] - acc['statistical']}
-    if dtw or dtw_template:
+    if dtw or dtw_template or hmm:
         tr, te = train_test_split(np.arange(len(y)), test_size=test_size, random_state=random_state, stratify=y)
         lengths = np.asarray(lengths)
         if 'KNN' in results:
@@ -78,7 +81,8 @@ def compare(data_dir=None, classifiers=None, test_size=0.2, random_state=42, dtw
             knn = create_classifier(kind, **params).fit(Xs_tr, y_tr)
             stat_acc = float(knn.evaluate(Xs_te, y_te)['accuracy'])
         rows = ([('KNN-DTW', 'dtw_knn', {'n_neighbors': 3})] if dtw else []) + \
-               ([('DTW-template', 'dtw_template', {})] if dtw_template else [])
+               ([('DTW-template', 'dtw_template', {})] if dtw_template else []) + \
+               ([('HMM', 'hmm', {})] if hmm else [])
         for name, kind, params in rows:
             clf = create_classifier(kind, **params).fit(X_seq[tr], y[tr], lengths=lengths[tr])
             seq_acc = float(clf.evaluate(X_seq[te], y[te], lengths=lengths[te])['accuracy'])

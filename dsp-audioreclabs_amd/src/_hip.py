@@ -38,7 +38,8 @@ EXPORTS = ("dsp_extract_lds_bytes", "dsp_extract_fast_layout", "dsp_extract_feat
            "dsp_svc_workspace_uncertified_offset", "dsp_svc_launch_parts", "dsp_svc_predict",
            "dsp_gnb_fit", "dsp_gnb_workspace_bytes", "dsp_gnb_predict", "dsp_tree_workspace_bytes",
            "dsp_tree_lds_nodes", "dsp_tree_predict", "dsp_dtw_workspace_bytes", "dsp_dtw_pairwise",
-           "dsp_dtw_knn", "dsp_dtw_align_workspace_bytes", "dsp_dtw_align", "dsp_dtw_dba_update")
+           "dsp_dtw_knn", "dsp_dtw_align_workspace_bytes", "dsp_dtw_align", "dsp_dtw_dba_update",
+           "dsp_hmm_workspace_bytes", "dsp_hmm_score", "dsp_hmm_align", "dsp_hmm_accumulate")
 DSP_WAV_OTHER, DSP_WAV_S16_MONO, DSP_WAV_U8_MONO = 0, 1, 2
 
 _lib = None
@@ -153,6 +154,18 @@ def load_library(path=LIB_PATH):
         L.dsp_dtw_align.argtypes = [vp, vp, i64, i32, vp, vp, i64, i32, i32, i32, vp, vp, i64, vp, vp, vp, vp, sz, vp]
         L.dsp_dtw_dba_update.restype = i32
         L.dsp_dtw_dba_update.argtypes = [vp, vp, i64, i32, vp, vp, i64, i32, i32, i32, vp, vp, i64, vp, vp, vp, sz, vp]
+    if hasattr(L, "dsp_hmm_score"):  # (older A/B variants lack the HMM)
+        model = [vp, vp, vp, vp, vp, vp, i64, i32]  # mu, w, g, stay, adv, n_states, C, Smax
+        seqs = [vp, vp, i64, i32, i32]  # x, len, N, T, F
+        L.dsp_hmm_workspace_bytes.restype = sz
+        L.dsp_hmm_workspace_bytes.argtypes = [i64, i64, i64, i32, i32, i32]
+        L.dsp_hmm_score.restype = i32
+        L.dsp_hmm_score.argtypes = model + seqs + [vp, vp, vp, sz, vp]
+        L.dsp_hmm_align.restype = i32
+        L.dsp_hmm_align.argtypes = model + seqs + [vp, vp, i64, vp, vp, vp, sz, vp]
+        L.dsp_hmm_accumulate.restype = i32
+        L.dsp_hmm_accumulate.argtypes = ([vp, vp, vp, i64, i32] + seqs + [vp, vp, i64, vp, vp, dbl, vp, vp, vp, vp, vp,
+                                                                         vp, sz, vp])
     _lib = L
     return L
 

@@ -31,6 +31,9 @@ sequence classifier) is k-NN under dynamic time warping on the per-frame sequenc
 dsp_dtw_knn): an exact fp64 distance, the KNN's voting and tie rules.
 ``TemplateClassifier`` / ``create_classifier('dtw_template')`` keeps one DBA template per class instead
 of the training set (csrc/dtw_align.hip, dsp_dtw_dba_update).
+``HmmClassifier`` / ``create_classifier('hmm')`` keeps one left-to-right Gaussian HMM per class, trained
+by Viterbi re-estimation (csrc/hmm.hip, dsp_hmm_score / dsp_hmm_align / dsp_hmm_accumulate, DESIGN.md
+§4.10): scores, state paths and re-estimated models defined bit for bit.
 
 ``MLPTrainer`` (models.py:109-221) trains the reference's MLP with the fused on-device trainer
 (csrc/mlp.hip: dsp_mlp_train / dsp_mlp_predict) -- the whole serial SGD loop of
@@ -399,6 +402,100 @@ class TemplateClassifier(SequenceClassifier):
         return self
 
 
+class HmmClassifier(SequenceClassifier):
+    """One left-to-right Gaussian hidden Markov model per class, trained by Viterbi re-estimation
+    (segmental k-means), and the label of the model with the best state path -- the textbook step
+    after DTW templates: a mean and a variance per state, and a cost for staying in a state, which
+    models duration.  csrc/hmm.hip (dsp_hmm_score, dsp_hmm_align, dsp_hmm_accumulate).
+    Input handling and normalisation are ``SequenceClassifier``'s.
+
+    n_states     states per model: an int, or one value per class (in the order of the sorted class
+                 values), each in 1 .. 32.
+    n_iter       rounds of align -> accumulate -> rebuild after the uniform start; training stops
+                 early when a round changes no segment boundary.
+    var_floor    lower bound of every variance (normalised units).
+    trans_floor  p_stay is clamped to [trans_floor, 1 - trans_floor].
+    A training sequence shorter than its class's n_states is left out of that class's statistics; a
+    class none of whose members is long enough raises ValueError at ``fit``.  ``predict`` raises
+    ValueError for a query with fewer frames than every model has states (``score_samples`` returns
+    its row of +inf).
+    After ``fit``: model_ (``pipeline.HmmModelSet``: mean, var, w, g, stay, adv, n_states), totals_
+    float64 [rounds run, C] (row t: each class's sum of its members' scores under the model round t
+    started from), n_iter_ the rounds run.
+    No CPU path: ``fit`` and ``predict`` raise HipError without a HIP device (constructing needs none).
+    """
+
+    def __init__(self, n_states=5, n_iter=10, var_floor=1e-3, trans_floor=1e-3, normalize=True):
+        super().__init__(n_neighbors=1, window=None, normalize=normalize)
+        from .pipeline import HMM_MAX_STATES
+        states = np.asarray(n_states)
+        if states.ndim > 1 or states.size < 1 or not np.issubdtype(states.dtype, np.integer):
+            raise ValueError("n_states must be an int or one int per class")
+        if states.min() < 1 or states.max() > HMM_MAX_STATES:
+            raise ValueError("n_states must lie in [1, %d]" % HMM_MAX_STATES)
+        self.n_states = int(states) if states.ndim == 0 else states.astype(np.int32)
+        self.n_iter, self.var_floor, self.trans_floor = int(n_iter), float(var_floor), float(trans_floor)
+        if self.n_iter < 0 or not self.var_floor > 0.0 or not np.isfinite(self.var_floor):
+            raise ValueError("n_iter must be >= 0 and var_floor a positive number")
+        if not 0.0 < self.trans_floor < 0.5:
+            raise ValueError("trans_floor must lie in (0, 0.5)")
+
+    def fit(self, X, y, lengths=None):
+        from .pipeline import HmmModelSet, HmmUpdater, hmm_uniform_segmentation
+        X, n, codes = self._training_set(X, y, lengths)
+        C, F = len(self.classes_), X.shape[2]
+        states = np.full(C, self.n_states, np.int32) if np.ndim(self.n_states) == 0 else self.n_states
+        if len(states) != C:
+            raise ValueError("%d n_states for %d classes" % (len(states), C))
+        Smax = int(states.max())
+        order = np.argsort(codes, kind="stable")  # each class's members in training order
+        start = np.concatenate([[0], np.cumsum(np.bincount(codes, minlength=C))])
+        longest = np.array([n[order[start[c]:start[c + 1]]].max() for c in range(C)])
+        if (longest < states).any():
+            c = int(np.argmax(longest < states))
+            raise ValueError("class %r has no sequence of at least n_states = %d frames" % (self.classes_[c], states[c]))
+        updater = HmmUpdater(X, n, start, order, check_finite=False)
+        seg = hmm_uniform_segmentation(n[order], states[codes[order]], Smax)
+        zeros = np.zeros((C, Smax, F))
+        stats = updater.accumulate(zeros, zeros, states, seg, np.zeros(len(order)), self.var_floor)
+        model = HmmModelSet(*stats[:4], states, self.trans_floor)
+        totals = []
+        for _ in range(self.n_iter):
+            score, new_seg = updater.align(model)
+            stats = updater.accumulate(model.mean, model.var, states, new_seg, score, self.var_floor)
+            totals.append(stats[4].cpu().numpy())
+            model = HmmModelSet(*stats[:4], states, self.trans_floor, prev=model)
+            new_seg = new_seg.cpu().numpy()
+            same = np.array_equal(new_seg, seg)
+            seg = new_seg
+            if same:
+                break
+        self.model_, self.n_iter_ = model, len(totals)
+        self.totals_ = np.array(totals, dtype=np.float64).reshape(len(totals), C)
+        return self
+
+    def _scores(self, X, lengths, with_labels):
+        from .pipeline import hmm_score
+        Xq, nq = _as_padded(X, lengths)
+        if Xq.shape[2] != self.model_.shape[2]:
+            raise ValueError("X has %d feature channels, the fitted models %d" % (Xq.shape[2], self.model_.shape[2]))
+        return hmm_score(self.model_, self._scale(Xq, nq), nq, with_labels=with_labels, check_finite=False)
+
+    def score_samples(self, X, lengths=None):
+        """float64 [n, C]: each sequence's negative log-likelihood along its best state path under each
+        class's model (+inf where the sequence has fewer frames than the model has states)."""
+        return self._scores(X, lengths, False)[0].cpu().numpy()
+
+    def kneighbors(self, X, lengths=None):
+        raise NotImplementedError("an HMM classifier keeps no training sequences")
+
+    def predict(self, X, lengths=None):
+        label = self._scores(X, lengths, True)[1].cpu().numpy()
+        if (label < 0).any():
+            raise ValueError("sequence %d has fewer frames than every model has states" % int(np.argmax(label < 0)))
+        return self.classes_[label]
+
+
 # ==================== MLP (models.py:77-221) ====================
 
 def _build_network(input_size, hidden_layers, num_classes, dropout):
@@ -665,8 +762,8 @@ def fit_mlp_models(X_train, y_train, input_size, hidden_layers, num_classes, lea
 
 
 def create_classifier(classifier_type, **kwargs):
-    """models.py:226-246.  'mlp' takes MLPTrainer's arguments; 'dtw_knn' and 'dtw_template' (extensions) are the
-    SequenceClassifier and the TemplateClassifier.  A bare ``create_classifier('mlp')``
+    """models.py:226-246.  'mlp' takes MLPTrainer's arguments; 'dtw_knn', 'dtw_template' and 'hmm' (extensions) are the
+    SequenceClassifier, the TemplateClassifier and the HmmClassifier.  A bare ``create_classifier('mlp')``
     raises NotImplementedError naming them (the reference fails there with a TypeError)."""
     if classifier_type in ['knn', 'naive_bayes', 'decision_tree', 'svm']:
         return TraditionalClassifier(classifier_type, **kwargs)
@@ -674,6 +771,8 @@ def create_classifier(classifier_type, **kwargs):
         return SequenceClassifier(**kwargs)
     if classifier_type == 'dtw_template':
         return TemplateClassifier(**kwargs)
+    if classifier_type == 'hmm':
+        return HmmClassifier(**kwargs)
     if classifier_type == 'mlp':
         if not kwargs:
             raise NotImplementedError("create_classifier('mlp') needs input_size, hidden_layers and num_classes "

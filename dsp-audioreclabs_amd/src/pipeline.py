@@ -467,6 +467,194 @@ def dtw_barycenter(seqs, lengths, init, n_iter=10, window=None, check_finite=Tru
     return tmpl[0].cpu().numpy(), np.array(inertia)
 
 
+HMM_MAX_STATES = 32  # states of one model at most (csrc/hmm.hip keeps them in registers)
+
+
+class HmmModelSet:
+    """C left-to-right Gaussian HMMs padded to Smax states, in the form ``dsp_hmm_score`` reads
+    (include/dsp_audiorec.h): mean, var, w [C, Smax, F], g, stay, adv [C, Smax] float64 and n_states
+    int32 [C], numpy arrays on the host.  This is the only place a logarithm is taken:
+        w = 0.5 / var;  g = 0.5 * (log(2 pi var_0) + log(2 pi var_1) + ...)    channels in ascending order
+        p_stay = (cnt - n_valid) / cnt, clamped to [trans_floor, 1 - trans_floor]
+        stay = -log(p_stay);  adv = -log(1 - p_stay)
+    Rows s >= n_states[c] are zeros.  A model with n_valid == 0 keeps ``prev``'s stay / adv (p_stay = 0.5
+    without ``prev``)."""
+
+    def __init__(self, mean, var, cnt, n_valid, n_states, trans_floor=1e-3, prev=None):
+        mean, var = (np.asarray(v.cpu().numpy() if hasattr(v, "cpu") else v, dtype=np.float64) for v in (mean, var))
+        cnt, n_valid, n_states = (np.asarray(v.cpu().numpy() if hasattr(v, "cpu") else v).astype(np.int64)
+                                  for v in (cnt, n_valid, n_states))
+        if mean.ndim != 3 or var.shape != mean.shape or cnt.shape != mean.shape[:2]:
+            raise ValueError("mean and var must be [C, Smax, F] and cnt [C, Smax]")
+        C, Smax, _ = mean.shape
+        if n_states.shape != (C,) or n_valid.shape != (C,) or Smax > HMM_MAX_STATES:
+            raise ValueError("n_states and n_valid must be [C], Smax <= %d" % HMM_MAX_STATES)
+        if C and (n_states.min() < 1 or n_states.max() > Smax):
+            raise ValueError("n_states must lie in [1, %d]" % Smax)
+        if not 0.0 < trans_floor < 0.5:
+            raise ValueError("trans_floor must lie in (0, 0.5)")
+        valid = np.arange(Smax)[None, :] < n_states[:, None]
+        v = np.where(valid[:, :, None], var, 1.0)
+        if not (np.isfinite(mean).all() and np.isfinite(v).all() and (v > 0).all()):
+            raise ValueError("means must be finite and variances finite and positive")
+        self.n_states = n_states.astype(np.int32)
+        self.mean = np.where(valid[:, :, None], mean, 0.0)
+        self.var = np.where(valid[:, :, None], var, 0.0)
+        self.w = np.where(valid[:, :, None], 0.5 / v, 0.0)
+        self.g = np.where(valid, 0.5 * np.cumsum(np.log((2.0 * np.pi) * v), axis=2)[:, :, -1], 0.0)
+        seen = valid & (cnt > 0) & (n_valid[:, None] > 0)
+        cf = np.where(seen, cnt, 2).astype(np.float64)
+        p = (cf - np.where(seen, n_valid[:, None], 1).astype(np.float64)) / cf
+        p = np.minimum(np.maximum(p, trans_floor), 1.0 - trans_floor)
+        stay, adv = -np.log(p), -np.log(1.0 - p)
+        if prev is not None:
+            keep = (n_valid == 0)[:, None]
+            stay, adv = np.where(keep, prev.stay, stay), np.where(keep, prev.adv, adv)
+        self.stay, self.adv = np.where(valid, stay, 0.0), np.where(valid, adv, 0.0)
+        self._dev = None
+
+    @property
+    def shape(self):
+        return self.mean.shape
+
+    def on_device(self, device):
+        """(mu, w, g, stay, adv, n_states) as device tensors, uploaded once."""
+        import torch
+        if self._dev is None or self._dev[0].device != torch.device(device):
+            self._dev = tuple(_as_device(a, torch.float64, device) for a in (self.mean, self.w, self.g, self.stay, self.adv))
+            self._dev += (_as_device(self.n_states, torch.int32, device),)
+        return self._dev
+
+
+def _hmm_ws(ws, C, N, P, T, F, Smax, device):
+    import torch
+    nbytes = _hip.lib().dsp_hmm_workspace_bytes(C, N, P, T, F, Smax)
+    if nbytes == 0:
+        raise ValueError("unsupported HMM shape (1 <= F <= 8, 1 <= T <= 1024, 1 <= Smax <= %d)" % HMM_MAX_STATES)
+    if ws is None or ws.numel() < nbytes:
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return ws
+
+
+def _hmm_model_args(models, F, device):
+    C, Smax, Fm = models.shape
+    if Fm != F:
+        raise ValueError("sequences of %d feature channels against models of %d" % (F, Fm))
+    return [_hip.ptr(t) for t in models.on_device(device)] + [C, Smax]
+
+
+def hmm_score(models, seqs, lengths, with_labels=False, check_finite=True, _ws=None):
+    """Viterbi scores (include/dsp_audiorec.h: dsp_hmm_score) of the padded sequences [N, T, F] under
+    every model of the ``HmmModelSet``: (score float64 [N, C], the negative log-likelihood of the best
+    state path, +inf where the sequence is shorter than the model; label int32 [N] or None: the
+    smallest score's model, -1 when every score is +inf) on the device."""
+    import torch
+    d = _hip.require_device()
+    x, n = _dtw_operand(seqs, lengths, d, check_finite)
+    N, T, F = x.shape
+    margs = _hmm_model_args(models, F, d)
+    C, Smax = margs[-2:]
+    score = torch.empty((N, C), dtype=torch.float64, device=d)
+    label = torch.empty(N, dtype=torch.int32, device=d) if with_labels else None
+    if N > 0:
+        ws = _hmm_ws(_ws, C, N, 0, T, F, Smax, d)
+        rc = _hip.lib().dsp_hmm_score(*margs, _hip.ptr(x), _hip.ptr(n), N, T, F, _hip.ptr(score), _hip.ptr(label),
+                                      _hip.ptr(ws), ws.numel(), _hip.stream_handle(d))
+        _hip.check(rc, "dsp_hmm_score")
+    return score, label
+
+
+class HmmUpdater:
+    """The sequences of a Viterbi training run uploaded once with their CSR class lists (one group per
+    model); the workspace is held across iterations.  ``align`` is one ``dsp_hmm_align`` call for all
+    models, ``accumulate`` one ``dsp_hmm_accumulate`` call."""
+
+    def __init__(self, seqs, lengths, group_start, members, check_finite=True):
+        import torch
+        self.device = d = _hip.require_device()
+        self.seqs, self.len_s = _dtw_operand(seqs, lengths, d, check_finite)
+        self.N, self.T, self.F = self.seqs.shape
+        self.C = len(group_start) - 1
+        start, members = _dtw_groups((group_start, members), None, self.C, self.N)
+        self.P = int(members.size)
+        self.start, self.members = _as_device(start, torch.int32, d), _as_device(members, torch.int32, d)
+        self._ws = None
+
+    def _workspace(self, Smax):
+        self._ws = _hmm_ws(self._ws, self.C, self.N, self.P, self.T, self.F, Smax, self.device)
+        return self._ws
+
+    def align(self, models, with_seg=True):
+        """(score float64 [P], seg int32 [P, Smax] or None) of every listed pair."""
+        import torch
+        d = self.device
+        margs = _hmm_model_args(models, self.F, d)
+        C, Smax = margs[-2:]
+        if C != self.C:
+            raise ValueError("%d models for %d groups" % (C, self.C))
+        score = torch.empty(self.P, dtype=torch.float64, device=d)
+        seg = torch.empty((self.P, Smax), dtype=torch.int32, device=d) if with_seg else None
+        if self.P > 0 and C > 0:
+            ws = self._workspace(Smax)
+            rc = _hip.lib().dsp_hmm_align(*margs, _hip.ptr(self.seqs), _hip.ptr(self.len_s), self.N, self.T, self.F,
+                                          _hip.ptr(self.start), _hip.ptr(self.members), self.P, _hip.ptr(score),
+                                          _hip.ptr(seg), _hip.ptr(ws), ws.numel(), _hip.stream_handle(d))
+            _hip.check(rc, "dsp_hmm_align")
+        return score, seg
+
+    def accumulate(self, mu_prev, var_prev, n_states, seg, score, var_floor=1e-3):
+        """The re-estimation from a given segmentation: (mean, var float64 [C, Smax, F], cnt int32
+        [C, Smax], n_valid int32 [C], total float64 [C]) on the device."""
+        import torch
+        d = self.device
+        mu_prev, var_prev = _as_device(mu_prev, torch.float64, d), _as_device(var_prev, torch.float64, d)
+        n_states, seg = _as_device(n_states, torch.int32, d).reshape(-1), _as_device(seg, torch.int32, d)
+        score = _as_device(score, torch.float64, d).reshape(-1)
+        if mu_prev.dim() != 3 or var_prev.shape != mu_prev.shape:
+            raise ValueError("mu_prev and var_prev must be [C, Smax, F]")
+        C, Smax, F = mu_prev.shape
+        if C != self.C or F != self.F or n_states.numel() != C or tuple(seg.shape) != (self.P, Smax) or score.numel() != self.P:
+            raise ValueError("models [%d, %d, %d], seg %s for %d groups, %d pairs of %d channels"
+                             % (C, Smax, F, tuple(seg.shape), self.C, self.P, self.F))
+        mean, var = torch.empty_like(mu_prev), torch.empty_like(var_prev)
+        cnt = torch.empty((C, Smax), dtype=torch.int32, device=d)
+        n_valid = torch.empty(C, dtype=torch.int32, device=d)
+        total = torch.empty(C, dtype=torch.float64, device=d)
+        if C > 0:
+            ws = self._workspace(Smax)
+            rc = _hip.lib().dsp_hmm_accumulate(_hip.ptr(mu_prev), _hip.ptr(var_prev), _hip.ptr(n_states), C, Smax,
+                                               _hip.ptr(self.seqs), _hip.ptr(self.len_s), self.N, self.T, F,
+                                               _hip.ptr(self.start), _hip.ptr(self.members), self.P, _hip.ptr(seg),
+                                               _hip.ptr(score), float(var_floor), _hip.ptr(mean), _hip.ptr(var),
+                                               _hip.ptr(cnt), _hip.ptr(n_valid), _hip.ptr(total), _hip.ptr(ws), ws.numel(),
+                                               _hip.stream_handle(d))
+            _hip.check(rc, "dsp_hmm_accumulate")
+        return mean, var, cnt, n_valid, total
+
+
+def hmm_align(models, seqs, lengths, groups=None, assign=None, with_seg=True, check_finite=True):
+    """Viterbi state paths (include/dsp_audiorec.h: dsp_hmm_align) of the padded sequences
+    seqs[members[p]] under model c, the pairs given as the CSR ``groups=(group_start [C + 1], members
+    [P])`` or as ``assign`` [N] (the model of each sequence, -1 to skip).  Returns (score float64 [P], seg
+    int32 [P, Smax] or None, group_start, members) on the device: seg[p, s] is the first frame of state
+    s (-1 behind the model's states, and everywhere for a pair whose score is +inf)."""
+    N = len(lengths)
+    start, members = _dtw_groups(groups, assign, models.shape[0], N)
+    up = HmmUpdater(seqs, lengths, start, members, check_finite)
+    score, seg = up.align(models, with_seg)
+    return score, seg, up.start, up.members
+
+
+def hmm_uniform_segmentation(lengths, n_states, Smax):
+    """The start of Viterbi training: state s of a pair with n frames and S states owns the frames
+    floor(s n / S) .. floor((s + 1) n / S) - 1 (integer arithmetic) -> seg int32 [P, Smax]; -1 behind the
+    model's states, and everywhere for a pair with n < S."""
+    n, S = (np.asarray(v).astype(np.int64).reshape(-1) for v in (lengths, n_states))
+    s = np.arange(int(Smax), dtype=np.int64)[None, :]
+    seg = (s * n[:, None]) // np.maximum(S, 1)[:, None]
+    return np.where((s < S[:, None]) & (n >= S)[:, None], seg, -1).astype(np.int32)
+
+
 class SvcIndex:
     """A fitted ``sklearn.svm.SVC(kernel='rbf')`` uploaded once for ``dsp_svc_predict``
     (csrc/svm.hip): libsvm's own arrays -- support_vectors_, _n_support, _dual_coef_, _intercept_,

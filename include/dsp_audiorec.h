@@ -36,7 +36,7 @@ extern "C" {
                               5: queue_ws is 4 KiB (each counter on its own 256-B line);
                               6: the extraction entry points take out_stride (packed result rows);
                                  dsp_knn_classify takes flags (DSP_KNN_REF_READY).
-                              Still 6 with the dsp_mlp_*, dsp_svc_*, dsp_gnb_*, dsp_tree_* and dsp_dtw_* (dsp_dtw_align, dsp_dtw_dba_update included) entry points: new symbols only, no
+                              Still 6 with the dsp_mlp_*, dsp_svc_*, dsp_gnb_*, dsp_tree_* and dsp_dtw_* (dsp_dtw_align, dsp_dtw_dba_update included) and dsp_hmm_* entry points: new symbols only, no
                               existing signature or meaning changed, so callers built against 6 keep
                               working (a binding that needs them checks for the symbols) */
 
@@ -505,6 +505,79 @@ int dsp_dtw_dba_update(const double *tmpl, const int32_t *len_t, int64_t C, int 
                        const int32_t *len_s, int64_t N, int Ts, int F, int window, const int32_t *group_start,
                        const int32_t *members, int64_t P, double *tmpl_out, double *inertia, void *workspace,
                        size_t workspace_bytes, void *stream);
+
+/*
+ * Left-to-right Gaussian hidden Markov models on the frame sequences, in the negative-log domain,
+ * with the pieces of Viterbi training (segmental k-means).  csrc/hmm.hip, DESIGN.md §4.10.  Every
+ * output is defined bit for bit: the device computes fp64 subtract, multiply, add, min and (in the
+ * re-estimation) divide in the order below, each operation rounded, no FMA; the logarithms are the
+ * caller's, taken when the model is built.
+ *
+ * Sequences: x float64 [N, T, F] padded row-major with len int32 [N], 1 <= F <= 8, 1 <= T <= 1024
+ *   (the DTW plan above).
+ * Model set: C <= 2^20 models padded to Smax states, 1 <= n_states[c] <= Smax <= 32: mu, w float64
+ *   [C, Smax, F], g, stay, adv float64 [C, Smax], n_states int32 [C].  All finite or +inf, never NaN,
+ *   never -inf (w = 0.5 / var, g = 0.5 sum_f log(2 pi var_f), stay = -log p_stay,
+ *   adv = -log(1 - p_stay)); adv[c, S-1] is never read.
+ * Recurrence, for a sequence of length n and a model of S states:
+ *     e(t,s) = g[s];  for f ascending:  d = x[t,f] - mu[s,f];  e = e + w[s,f] * (d * d)
+ *     V(0,0) = e(0,0);  V(0,s>0) = +inf
+ *     a = V(t-1,s) + stay[s];  b = V(t-1,s-1) + adv[s-1]        (b = +inf at s = 0)
+ *     V(t,s) = e(t,s) + min(a, b)
+ *     score  = V(n-1, S-1)
+ *   score is +inf when n < S, and also when n < 1, n > T or n_states[c] is outside 1 .. Smax.
+ * Path: walk back from (n-1, S-1); the predecessor is the advance (t-1, s-1) iff b < a strictly, so
+ *   ties stay.  Returned as seg int32 [P, Smax], seg[s] the first frame of state s: seg[0] = 0, seg is
+ *   strictly increasing, entries s >= S are -1; every entry of a pair whose score is +inf is -1.
+ * Pairs (dsp_hmm_align, dsp_hmm_accumulate): dsp_dtw_align's CSR list over the models -- group_start
+ *   int32 [C + 1], members int32 [P]; a members entry outside [0, N) counts as an invalid length and
+ *   is never read through; a sequence may appear under several models; a group may be empty.
+ *
+ * dsp_hmm_score: every sequence against every model, score float64 [N, C]; label int32 [N] the model
+ *   index of the smallest score, ties to the smaller index, -1 when every score is +inf.  Either
+ *   output may be NULL.
+ * dsp_hmm_align: score float64 [P] and seg int32 [P, Smax] of the listed pairs; either may be NULL
+ *   (without seg no direction bit is stored and no path is walked).
+ * dsp_hmm_accumulate: the re-estimation of every model from a GIVEN seg [P, Smax] and score [P] (the
+ *   output of dsp_hmm_align, or a segmentation of the caller's, e.g. the uniform start: state s =
+ *   frames floor(s n / S) .. floor((s+1) n / S) - 1 for members with n >= S, -1 rows otherwise).  A
+ *   member is valid when its index and length are and its seg row is well formed for its model
+ *   (seg[0] = 0, strictly increasing over the S states, seg[S-1] < n); other members are skipped.
+ *   For model c with valid members k0 < k1 < ... in list order, state s owning the member's frames
+ *   beg = seg[s] .. end = seg[s+1] - 1 (the last state up to n - 1):
+ *     X_k[s,f] = x[beg,f] + ... + x[end,f]        left to right; Q_k likewise over the products x * x
+ *     accX = X_k0;  accX = accX + X_k  ...        in list order; accQ likewise
+ *     cnt[s]   = sum_k (end - beg + 1)            integer
+ *     mean = accX / cnt;   var = max(accQ / cnt - mean * mean, var_floor)
+ *     total = score_k0 + score_k1 + ...           in list order;  n_valid = number of valid members
+ *   Outputs mean, var float64 [C, Smax, F] (neither may be mu_prev / var_prev), cnt int32 [C, Smax],
+ *   n_valid int32 [C], total float64 [C].  Rows s >= S are zeros.  A model with no valid member or
+ *   an n_states outside 1 .. Smax is copied bit for bit from mu_prev / var_prev, with total 0.0,
+ *   n_valid 0 and cnt 0.  Every valid member visits every state, so the transition estimate needs
+ *   only these: p_stay[s] = (cnt[s] - n_valid) / cnt[s].
+ * workspace  device scratch of dsp_hmm_workspace_bytes(C, N, P, T, F, Smax) bytes (0: sizes outside
+ *   the plan; P = 0 for dsp_hmm_score): the model set repacked as one record per state, one 32-bit
+ *   direction word per row and lane for each resident wave (at most 256 MiB), N x C scores (labels
+ *   without scores), and for the re-estimation the sums of one chunk of pairs (at most 128 MiB) and
+ *   the models' counts.  Nothing in it is carried from one call to the next.
+ * All three check their host arguments before any launch (DSP_ERR_ARGS, DSP_ERR_WORKSPACE), return
+ * DSP_OK with nothing to do, make no host synchronisation and no allocation, and write only to their
+ * outputs and the workspace, on the caller's stream.
+ */
+size_t dsp_hmm_workspace_bytes(int64_t C, int64_t N, int64_t P, int T, int F, int Smax);
+int dsp_hmm_score(const double *mu, const double *w, const double *g, const double *stay, const double *adv,
+                  const int32_t *n_states, int64_t C, int Smax, const double *x, const int32_t *len, int64_t N,
+                  int T, int F, double *score, int32_t *label, void *workspace, size_t workspace_bytes,
+                  void *stream);
+int dsp_hmm_align(const double *mu, const double *w, const double *g, const double *stay, const double *adv,
+                  const int32_t *n_states, int64_t C, int Smax, const double *x, const int32_t *len, int64_t N,
+                  int T, int F, const int32_t *group_start, const int32_t *members, int64_t P, double *score,
+                  int32_t *seg, void *workspace, size_t workspace_bytes, void *stream);
+int dsp_hmm_accumulate(const double *mu_prev, const double *var_prev, const int32_t *n_states, int64_t C,
+                       int Smax, const double *x, const int32_t *len, int64_t N, int T, int F,
+                       const int32_t *group_start, const int32_t *members, int64_t P, const int32_t *seg,
+                       const double *score, double var_floor, double *mean, double *var, int32_t *cnt,
+                       int32_t *n_valid, double *total, void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * Batch WAV reader -- host only (no GPU, no stream): the file side of load_wav
