@@ -105,10 +105,11 @@ def forward(params, x, masks=None, scale=1.0):
 
 
 def train(packed0, D, hidden, C, X, y, perm, batch_size, lr, seed=0, p=0.0, dtype=torch.float64, step0=0,
-          variant=None):
+          variant=None, keep_logits=False):
     """The reference's fit loop.  Returns dict(params, m, v [packed, numpy of `dtype`], loss_hist,
-    acc_hist [float64 per epoch], min_gap [per epoch: smallest top-2 gap of a train-mode logit row],
-    steps)."""
+    acc_hist [float64 per epoch], hits [int per epoch: the count acc_hist divides by N], min_gap [per
+    epoch: smallest top-2 gap of a train-mode logit row], steps), and with keep_logits also logits
+    [per epoch a list with every step's train-mode logits, float64 [rows, C]]."""
     dims = layer_dims(D, hidden, C)
     params = [t.requires_grad_(True) for t in unpack(packed0, dims, dtype)]
     Xt = torch.tensor(np.asarray(X, dtype=np.float32), dtype=dtype)  # FloatTensor(X_train)
@@ -122,9 +123,10 @@ def train(packed0, D, hidden, C, X, y, perm, batch_size, lr, seed=0, p=0.0, dtyp
     m = [torch.zeros_like(t) for t in params]
     v = [torch.zeros_like(t) for t in params]
     step = int(step0)
-    loss_hist, acc_hist, min_gap = [], [], []
+    loss_hist, acc_hist, hits, min_gap, logits = [], [], [], [], []
     for e in range(perm.shape[0]):
         epoch_loss, correct, nb, gap = 0.0, 0, 0, np.inf
+        logits.append([])
         for lo in range(0, N, batch_size):
             idx = torch.as_tensor(np.asarray(perm[e, lo:lo + batch_size]), dtype=torch.int64)
             xb, yb = Xt[idx], yt[idx]
@@ -150,6 +152,8 @@ def train(packed0, D, hidden, C, X, y, perm, batch_size, lr, seed=0, p=0.0, dtyp
                 opt.step()
             epoch_loss += loss.item()
             correct += int((out.detach().argmax(1) == yb).sum())
+            if keep_logits:
+                logits[-1].append(out.detach().double().numpy().copy())
             if out.shape[1] > 1:
                 top = torch.topk(out.detach().double(), 2, dim=1).values
                 gap = min(gap, float((top[:, 0] - top[:, 1]).min()))
@@ -157,12 +161,16 @@ def train(packed0, D, hidden, C, X, y, perm, batch_size, lr, seed=0, p=0.0, dtyp
             step += 1
         loss_hist.append(epoch_loss / nb)
         acc_hist.append(correct / N)
+        hits.append(correct)
         min_gap.append(gap)
     if not manual:
         m = [opt.state[t]['exp_avg'] for t in params]
         v = [opt.state[t]['exp_avg_sq'] for t in params]
-    return dict(params=pack(params), m=pack(m), v=pack(v), loss_hist=np.array(loss_hist),
-                acc_hist=np.array(acc_hist), min_gap=np.array(min_gap), steps=step)
+    out = dict(params=pack(params), m=pack(m), v=pack(v), loss_hist=np.array(loss_hist),
+               acc_hist=np.array(acc_hist), hits=np.array(hits, dtype=np.int64), min_gap=np.array(min_gap), steps=step)
+    if keep_logits:
+        out['logits'] = logits
+    return out
 
 
 def predict_logits(packed, D, hidden, C, X, dtype=torch.float64):
@@ -180,6 +188,9 @@ PARITY_SHAPES = {
     'odd_16': (15, [33, 17], 7, 16, 33),              # the last batch is one row
     'n_below_batch': (15, [33, 17], 7, 16, 7),        # N < batch_size
 }
+# the data seed of each shape: explicit, so that a new shape leaves the inputs of the others alone
+# (tests/golden/mlp_parity_inputs.npz pins them)
+PARITY_DATA_SEEDS = {'config_108': 11, 'n_below_batch': 12, 'odd_16': 13, 'tiny_4': 14}
 PARITY_EPOCHS = 3
 PARITY_LR = 1e-3
 PARITY_SEED = 1234
@@ -196,16 +207,22 @@ MARGIN = 16.0
 FLOOR = 1e-7
 
 
-def parity_inputs(name):
-    """(D, hidden, C, batch, N, X float32, y int32, perm int32 [E, N], packed0 float32)."""
-    D, hidden, C, batch, N = PARITY_SHAPES[name]
-    rng = np.random.default_rng(sorted(PARITY_SHAPES).index(name) + 11)
+def make_inputs(D, hidden, C, N, data_seed, init_seed=7, epochs=PARITY_EPOCHS):
+    """The data recipe every training case shares: (X float32 [N, D], y int32 [N], perm int32 [E, N],
+    packed0 float32)."""
+    rng = np.random.default_rng(data_seed)
     y = (np.arange(N) % C).astype(np.int32)
     rng.shuffle(y)
     centers = rng.normal(size=(C, D))
     X = (centers[y] + rng.normal(size=(N, D))).astype(np.float32)  # learnable, z-score-like scale
-    perm = np.stack([rng.permutation(N) for _ in range(PARITY_EPOCHS)]).astype(np.int32)
-    return D, hidden, C, batch, N, X, y, perm, init_packed(D, hidden, C, seed=7)
+    perm = np.stack([rng.permutation(N) for _ in range(epochs)]).astype(np.int32)
+    return X, y, perm, init_packed(D, hidden, C, seed=init_seed)
+
+
+def parity_inputs(name):
+    """(D, hidden, C, batch, N, X float32, y int32, perm int32 [E, N], packed0 float32)."""
+    D, hidden, C, batch, N = PARITY_SHAPES[name]
+    return (D, hidden, C, batch, N) + make_inputs(D, hidden, C, N, PARITY_DATA_SEEDS[name])
 
 
 _CACHE = {}
@@ -217,7 +234,7 @@ def parity_reference(name, p, dtype=torch.float64, variant=None):
     if key not in _CACHE:
         D, hidden, C, batch, N, X, y, perm, w0 = parity_inputs(name)
         _CACHE[key] = train(w0, D, hidden, C, X, y, perm, batch, PARITY_LR, seed=PARITY_SEED, p=p, dtype=dtype,
-                            variant=variant)
+                            variant=variant, keep_logits=True)
     return _CACHE[key]
 
 
@@ -226,6 +243,67 @@ def parity_bound(name, p, key='params'):
     a = parity_reference(name, p, torch.float64)[key]
     b = parity_reference(name, p, torch.float32)[key]
     return MARGIN * float(np.max(np.abs(a - b.astype(np.float64)))) + FLOOR
+
+
+# ---- per-tensor deviations ------------------------------------------------------------------
+def tensor_names(dims):
+    """W0, b0, W1, b1, ...: the state_dict() order of the packed layout."""
+    return [n % l for l in range(len(dims) - 1) for n in ('W%d', 'b%d')]
+
+
+def split_packed(packed, dims):
+    """The packed vector as views of its tensors, flat, in tensor_names(dims) order."""
+    packed = np.asarray(packed)
+    out, off = [], 0
+    for i, o in zip(dims[:-1], dims[1:]):
+        out += [packed[off:off + o * i], packed[off + o * i:off + o * i + o]]
+        off += o * i + o
+    assert off == packed.shape[0]
+    return out
+
+
+def per_tensor_deviation(a, b, dims):
+    """max |a - b| inside each tensor, float64 [2 * linear layers]."""
+    d = np.abs(np.asarray(a, dtype=np.float64) - np.asarray(b, dtype=np.float64))
+    return np.array([float(t.max()) for t in split_packed(d, dims)])
+
+
+def bound_per_tensor(ref64, ref32, dims, key='params'):
+    """MARGIN x (the fp32 CPU run's max deviation from the fp64 run, in that tensor) + FLOOR, for two
+    results of train()."""
+    return MARGIN * per_tensor_deviation(ref64[key], ref32[key], dims) + FLOOR
+
+
+def parity_bound_per_tensor(name, p, key='params'):
+    D, hidden, C = PARITY_SHAPES[name][:3]
+    return bound_per_tensor(parity_reference(name, p, torch.float64), parity_reference(name, p, torch.float32),
+                            layer_dims(D, hidden, C), key)
+
+
+def loss_bound(ref64, ref32):
+    """The loss history's bound: MARGIN x the fp32 CPU run's deviation + FLOOR, and 4 float32 roundings
+    of the value (it is stored as float32)."""
+    dev = float(np.max(np.abs(ref64['loss_hist'] - ref32['loss_hist'].astype(np.float64))))
+    return MARGIN * dev + FLOOR + 4 * 2.0 ** -24 * float(np.max(ref64['loss_hist']))
+
+
+def near_ties(ref64, ref32):
+    """(threshold [E], rows under it [E]) of two train(keep_logits=True) results.  An fp32 trainer within
+    MARGIN x the fp32 CPU run's own logit deviation + FLOOR of the fp64 logits can move each of a row's
+    two largest logits by that much, so a row decides its argmax differently only when its fp64 top-2
+    gap is under twice that.  Where no row is, the hit count of every epoch is exact."""
+    thr, cnt = [], []
+    for l64, l32 in zip(ref64['logits'], ref32['logits']):
+        dev = max(float(np.max(np.abs(a - b))) for a, b in zip(l64, l32))
+        t = 2 * (MARGIN * dev + FLOOR)
+        n = 0
+        for a in l64:
+            if a.shape[1] > 1:
+                top = np.sort(a, axis=1)
+                n += int(((top[:, -1] - top[:, -2]) < t).sum())
+        thr.append(t)
+        cnt.append(n)
+    return np.array(thr), np.array(cnt, dtype=np.int64)
 
 
 PREDICT_N = 1000
