@@ -30,17 +30,20 @@ CLASSIFIERS = {
 }
 
 
-def load_both_methods(data_dir=None, frame_length=None, frame_shift=None, window_type='hamming'):
-    """:27-122 -> (X_statistical [n, 15], X_sequences_padded [n, max_len, 2], y, lengths)."""
+def load_both_methods(data_dir=None, frame_length=None, frame_shift=None, window_type='hamming', pitch=False):
+    """:27-122 -> (X_statistical [n, 15], X_sequences_padded [n, max_len, 2], y, lengths); with
+    ``pitch`` [n, 20] and [n, max_len, 3], the f0 statistics and the per-frame f0 appended
+    (PCMDataset.extract_both)."""
     ds = PCMDataset(data_dir or config.DATA_DIR)
     X_stat, y, X_seq, lengths = ds.extract_both(frame_length or config.FRAME_LENGTH,
                                                 frame_shift or config.FRAME_SHIFT, window_type,
-                                                do_endpoint_detection=True, use_only_energy_zcr=True)
+                                                do_endpoint_detection=True, use_only_energy_zcr=True, pitch=pitch,
+                                                sample_rate=config.SAMPLE_RATE)
     return X_stat, X_seq, y, lengths
 
 
 def compare(data_dir=None, classifiers=None, test_size=0.2, random_state=42, dtw=False, dtw_template=False,
-            hmm=False):
+            hmm=False, pitch=False):
     """:124-214: each classifier on both feature sets, the reference's split and normalisation
     -> {classifier: {'statistical': acc, 'sequence': acc, 'diff': sequence - statistical}}.
     KNN on the flattened sequences (2 x max_frames columns) runs on the device like the 15-d
@@ -51,9 +54,11 @@ def compare(data_dir=None, classifiers=None, test_size=0.2, random_state=42, dtw
     dtw_template=True (an extension) adds the row 'DTW-template' beside it: the same, for the nearest
     of one DBA template per class (src.models.TemplateClassifier, its defaults).
     hmm=True (an extension) adds the row 'HMM' beside them: the same, for one left-to-right Gaussian
-    HMM per class (src.models.HmmClassifier, its defaults)."""
+    HMM per class (src.models.HmmClassifier, its defaults).
+    pitch=True (an extension): every row runs on the 20-d matrix (the 15 columns plus five f0 statistics)
+    and on the (E, ZCR, f0) sequences of the exact autocorrelation pitch track (src.pipeline.PitchTracker)."""
     from sklearn.model_selection import train_test_split
-    X_stat, X_seq, y, lengths = load_both_methods(data_dir)
+    X_stat, X_seq, y, lengths = load_both_methods(data_dir, pitch=pitch)
     X_flat = X_seq.reshape(len(X_seq), -1)
     Xs_tr, Xs_te, y_tr, y_te = train_test_split(X_stat, y, test_size=test_size, random_state=random_state,
                                                 stratify=y)

@@ -20,7 +20,7 @@ from glob import glob
 import numpy as np
 
 from .audio_processing import load_wav_pcm
-from .pipeline import FeatureExtractor
+from .pipeline import FeatureExtractor, PitchTracker, f0_statistics
 
 
 def list_dataset(data_dir):
@@ -221,9 +221,15 @@ class PCMDataset:
 
     def extract_both(self, frame_length, frame_shift, window_type='hamming', do_endpoint_detection=True,
                      use_only_energy_zcr=True, energy_high_ratio=0.5, energy_low_ratio=0.1,
-                     zcr_threshold_ratio=1.5):
+                     zcr_threshold_ratio=1.5, pitch=False, sample_rate=44100):
         """compare_feature_methods.py:43-115 in one fused launch: the statistical matrix and the
         padded sequence tensor of the same clips.
+
+        ``pitch=True`` adds the exact autocorrelation pitch track (``PitchTracker``, 60 .. 400 Hz at
+        ``sample_rate``): X_seq gains f0 as its last column (0.0 on unvoiced frames and in the
+        padding) and X_stat becomes [n_ok, 20], the 15 columns plus mean, std, max, min and median of
+        f0 over the clip's voiced frames (0.0 for a clip without one).  A dataset with 16-bit stereo
+        clips held as int32 channel sums raises ValueError then: the track takes int16 samples.
 
         -> (X_stat float64 [n_ok, 15], y [n_ok], X_seq float64 [n_ok, max_frames, 2|3], lengths
         [n_ok]).  The kernel writes each clip's per-frame (E, M, ZCR) rows into a zeroed
@@ -233,13 +239,30 @@ class PCMDataset:
         fx = FeatureExtractor(frame_length, frame_shift, window_type, do_endpoint_detection,
                               energy_high_ratio, energy_low_ratio, zcr_threshold_ratio,
                               return_sequences=True, device=self.device)
-        out = self._run(fx)
+        run = fx
+        if pitch:
+            import torch
+            if any(dp.dtype != torch.int16 for _, dp, _, _ in self.parts):
+                raise ValueError("extract_both(pitch=True): the pitch track takes int16 samples, and this dataset "
+                                 "holds 16-bit stereo clips as int32 channel sums")
+            tracker = PitchTracker(frame_length, frame_shift, sample_rate, device=self.device)
+
+            def run(dp, do, max_len):
+                o = dict(fx(dp, do, max_len=max_len))
+                track = tracker(dp, o, do, max_len=max_len)
+                o.update(f0=track["f0"], voiced=track["voiced"])
+                return o
+        out = self._run(run)
         ok = (out["status"] & 0xFF) == 0
         lengths = out["n_frames"].astype(np.int64)[ok]
         width = int(lengths.max()) if lengths.size else 0
         cols = [0, 2] if use_only_energy_zcr else [0, 1, 2]
         seq = out["seq"][ok][:, :width][:, :, cols].astype(np.float64)
         feat = out["feat"].astype(np.float64)[ok]
+        if pitch:
+            f0, voiced = out["f0"][ok][:, :width], out["voiced"][ok][:, :width]
+            seq = np.concatenate([seq, f0[:, :, None]], axis=2)
+            feat = np.concatenate([feat, f0_statistics(f0, voiced)], axis=1)
         return feat, self.labels[ok], seq, lengths
 
     def sweep(self, configs, **kw):

@@ -655,6 +655,107 @@ def hmm_uniform_segmentation(lengths, n_states, Smax):
     return np.where((s < S[:, None]) & (n >= S)[:, None], seg, -1).astype(np.int32)
 
 
+class PitchTracker:
+    """Launch plan for ``dsp_pitch_track`` (csrc/pitch.hip): the exact short-time
+    autocorrelation of every crop frame, the smallest lag of its maximum inside
+    [sample_rate // f0_max, sample_rate // f0_min] (clamped to [1, L - 1]), and the voicing decision and
+    f0 derived from them on the device.  It runs after a ``FeatureExtractor`` call, on that call's
+    device outputs.  The arguments are validated here, without a device."""
+
+    def __init__(self, frame_length, frame_shift, sample_rate, f0_min=60.0, f0_max=400.0, voicing=(3, 10),
+                 device=None):
+        for name, v in (("frame_length", frame_length), ("frame_shift", frame_shift), ("sample_rate", sample_rate)):
+            if isinstance(v, bool) or int(v) != v:
+                raise ValueError("%s must be an integer" % name)
+        self.L, self.S, self.sample_rate = int(frame_length), int(frame_shift), int(sample_rate)
+        if not 2 <= self.L <= 4096:
+            raise ValueError("frame_length must be in 2 .. 4096")
+        if self.S < 1 or self.sample_rate < 1:
+            raise ValueError("frame_shift and sample_rate must be positive")
+        f0_min, f0_max = float(f0_min), float(f0_max)
+        if not 0.0 < f0_min <= f0_max or not np.isfinite(f0_max):
+            raise ValueError("need 0 < f0_min <= f0_max")
+        try:
+            vnum, vden = voicing
+        except (TypeError, ValueError):
+            raise ValueError("voicing is a pair (vnum, vden)")
+        if any(isinstance(v, bool) or int(v) != v for v in (vnum, vden)) or not 1 <= vnum <= vden <= 1024:
+            raise ValueError("voicing needs integers 1 <= vnum <= vden <= 1024")
+        self.vnum, self.vden = int(vnum), int(vden)
+        self.lag_min = min(max(int(self.sample_rate // f0_max), 1), self.L - 1)
+        self.lag_max = min(max(int(self.sample_rate // f0_min), 1), self.L - 1)
+        self.device = device
+        self._ws = None
+
+    def frames(self, max_len):
+        """Width of the per-frame outputs for clips of up to max_len samples (the widest crop)."""
+        return 1 if max_len <= self.L else (int(max_len) - self.L + self.S - 1) // self.S + 1
+
+    def __call__(self, pcm, extracted, offsets=None, max_len=None):
+        """pcm, offsets: what the ``FeatureExtractor`` call was given (int16); ``extracted``: the dict
+        it returned.  -> dict of device tensors [B, frames(max_len)]: lag int32, peak and r0 int64,
+        voiced bool, f0 float64; zeros (False) behind a clip's frames and in the rows of failed clips."""
+        import torch
+        if self.device is None:
+            self.device = _hip.require_device()
+        d = self.device
+        if str(getattr(pcm, "dtype", "")) not in ("int16", "torch.int16"):
+            raise ValueError("the pitch track takes int16 samples (16-bit stereo channel sums in int32 are not supported)")
+        pcm = _as_device(pcm, torch.int16, d)
+        if offsets is None:
+            if pcm.dim() != 2:
+                raise ValueError("1-D packed pcm needs offsets")
+            B, N = pcm.shape
+            off = torch.arange(B + 1, dtype=torch.int64, device=d) * N
+            true_max = N
+        else:
+            off = _as_device(offsets, torch.int64, d)
+            B = off.numel() - 1
+            true_max = None
+        if max_len is None:
+            max_len = true_max if true_max is not None else (int(torch.max(off[1:] - off[:-1]).item()) if B > 0 else 1)
+        max_len = max(int(max_len), 1)
+        rows = extracted["rows"]
+        if rows.shape != (B, _hip.OUT_ROW_WORDS) or rows.dtype != torch.int32 or not rows.is_contiguous():
+            raise ValueError("extracted['rows'] must be the [B, 19] int32 rows of the same batch")
+        ld = self.frames(max_len)
+        lag = torch.zeros((B, ld), dtype=torch.int32, device=d)
+        peak = torch.zeros((B, ld), dtype=torch.int64, device=d)
+        r0 = torch.zeros((B, ld), dtype=torch.int64, device=d)
+        lib = _hip.lib()
+        nbytes = lib.dsp_pitch_workspace_bytes(B, max_len, self.L, self.S, self.lag_min, self.lag_max)
+        if nbytes == 0:
+            raise ValueError("outside the pitch plan")
+        if self._ws is None or self._ws.numel() < nbytes:
+            self._ws = torch.zeros(nbytes, dtype=torch.uint8, device=d)
+        rc = lib.dsp_pitch_track(_hip.ptr(pcm.reshape(-1)), _hip.ptr(off), B, max_len, self.L, self.S, self.lag_min,
+                                 self.lag_max, _hip.ptr(rows[:, 15:]), _hip.ptr(rows[:, 17:]), _hip.ptr(rows[:, 18:]),
+                                 _hip.OUT_ROW_WORDS, _hip.ptr(lag), _hip.ptr(peak), _hip.ptr(r0), ld,
+                                 _hip.ptr(self._ws), self._ws.numel(), _hip.stream_handle(d))
+        _hip.check(rc, "dsp_pitch_track")
+        voiced = (peak > 0) & (self.vden * peak >= self.vnum * r0)
+        rate = torch.tensor(float(self.sample_rate), dtype=torch.float64, device=d)
+        f0 = torch.where(voiced, rate / lag.clamp(min=1).to(torch.float64), torch.zeros((), dtype=torch.float64, device=d))
+        return dict(lag=lag, peak=peak, r0=r0, voiced=voiced, f0=f0)
+
+    def plain_frames(self):
+        """Frames of the last call that took the plain int64 path (one host sync)."""
+        import torch
+        return int(self._ws[:4].view(torch.int32).item())
+
+
+def f0_statistics(f0, voiced):
+    """mean, std, max, min, median of each row's f0 over its voiced frames (numpy, fp64, as
+    compute_statistics does) -> [n, 5]; 0.0 for a row without a voiced frame."""
+    f0, voiced = np.asarray(f0, np.float64), np.asarray(voiced, bool)
+    out = np.zeros((f0.shape[0], 5))
+    for i in range(f0.shape[0]):
+        v = f0[i][voiced[i]]
+        if v.size:
+            out[i] = [np.mean(v), np.std(v), np.max(v), np.min(v), np.median(v)]
+    return out
+
+
 class SvcIndex:
     """A fitted ``sklearn.svm.SVC(kernel='rbf')`` uploaded once for ``dsp_svc_predict``
     (csrc/svm.hip): libsvm's own arrays -- support_vectors_, _n_support, _dual_coef_, _intercept_,

@@ -36,7 +36,7 @@ extern "C" {
                               5: queue_ws is 4 KiB (each counter on its own 256-B line);
                               6: the extraction entry points take out_stride (packed result rows);
                                  dsp_knn_classify takes flags (DSP_KNN_REF_READY).
-                              Still 6 with the dsp_mlp_*, dsp_svc_*, dsp_gnb_*, dsp_tree_* and dsp_dtw_* (dsp_dtw_align, dsp_dtw_dba_update included) and dsp_hmm_* entry points: new symbols only, no
+                              Still 6 with the dsp_mlp_*, dsp_svc_*, dsp_gnb_*, dsp_tree_* and dsp_dtw_* (dsp_dtw_align, dsp_dtw_dba_update included) and dsp_hmm_* and dsp_pitch_* entry points: new symbols only, no
                               existing signature or meaning changed, so callers built against 6 keep
                               working (a binding that needs them checks for the symbols) */
 
@@ -578,6 +578,46 @@ int dsp_hmm_accumulate(const double *mu_prev, const double *var_prev, const int3
                        const int32_t *group_start, const int32_t *members, int64_t P, const int32_t *seg,
                        const double *score, double var_floor, double *mean, double *var, int32_t *cnt,
                        int32_t *n_valid, double *total, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Short-time autocorrelation pitch track -- the fourth classical time-domain feature next to energy,
+ * magnitude and ZCR, on the crop frames that dsp_extract_features found.  csrc/pitch.hip, DESIGN.md
+ * §4.11.  Every output is an exact integer; no floating point is involved.
+ *
+ * A clip is x[0..N) int16, its crop [st, en) and its frame count nf as dsp_extract_features wrote
+ * them, L = frame_length, S = frame_shift, 1 <= lag_min <= lag_max <= L - 1.
+ *   centring  c = floor((2 sum(x) + N) / (2 N))   the clip mean rounded half up, exact integers
+ *             y[n] = x[n] - c                     |y| <= 65535
+ *   frames    t = 0 .. nf - 1, frame_signal's frames, the last one zero-padded, no window:
+ *             f_t[i] = y[st + t S + i] if st + t S + i < en, else 0      0 <= i < L
+ *   r_t(tau)  = sum_{i=0}^{L-1-tau} f_t[i] f_t[i + tau]                  exact int64
+ *   lag[t]    the SMALLEST tau in [lag_min, lag_max] that maximises r_t(tau)
+ *   peak[t]   r_t(lag[t])
+ *   r0[t]     r_t(0)
+ * All three are written for every frame, voiced or not; an all-zero frame gives lag_min, 0, 0.
+ * Voicing and f0 are pure functions of these and are the caller's:
+ *   voiced = peak > 0 and vden * peak >= vnum * r0 (int64; 1 <= vnum <= vden <= 1024, default 3/10),
+ *   f0 = sample_rate / lag (one fp64 division), 0.0 where unvoiced.
+ *
+ * pcm, offsets  as dsp_extract_features (pcm 4-byte aligned is enough here).
+ * start_end, n_frames, status  that call's outputs, read on the device; out_stride as there (0: separate
+ *             arrays; 19: the packed rows pass straight in as rows + 15, rows + 17, rows + 18).
+ * lag int32, peak int64, r0 int64  [B, ld].  Frames t >= min(nf, ld) are left untouched, and so are the
+ *             rows of clips with status & 0xFF != 0, of clips longer than max_len and of clips whose
+ *             crop does not lie inside the clip (nothing is read outside a clip).
+ * workspace   device scratch of dsp_pitch_workspace_bytes(...) bytes (0: outside the plan -- B >= 0,
+ *             max_len >= 1, 2 <= L <= 4096, S >= 1, the lag range above); its first int32 is left
+ *             holding the number of frames answered by the plain int64 path (frames with a sample
+ *             y >= 32640 or y < -32896, whose high byte digit does not fit the i8 matrix cores).
+ * Host checks before the launch (DSP_ERR_ARGS, DSP_ERR_WORKSPACE); B = 0 returns DSP_OK without a
+ * launch; stream-ordered, no allocation, no copy, no synchronisation.
+ */
+size_t dsp_pitch_workspace_bytes(int B, int64_t max_len, int frame_length, int frame_shift, int lag_min,
+                                 int lag_max);
+int dsp_pitch_track(const int16_t *pcm, const int64_t *offsets, int B, int64_t max_len, int frame_length,
+                    int frame_shift, int lag_min, int lag_max, const int32_t *start_end,
+                    const int32_t *n_frames, const int32_t *status, int out_stride, int32_t *lag, int64_t *peak,
+                    int64_t *r0, int ld, void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * Batch WAV reader -- host only (no GPU, no stream): the file side of load_wav
