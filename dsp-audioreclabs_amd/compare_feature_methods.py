@@ -30,20 +30,21 @@ CLASSIFIERS = {
 }
 
 
-def load_both_methods(data_dir=None, frame_length=None, frame_shift=None, window_type='hamming', pitch=False):
+def load_both_methods(data_dir=None, frame_length=None, frame_shift=None, window_type='hamming', pitch=False, lpc=0):
     """:27-122 -> (X_statistical [n, 15], X_sequences_padded [n, max_len, 2], y, lengths); with
     ``pitch`` [n, 20] and [n, max_len, 3], the f0 statistics and the per-frame f0 appended
-    (PCMDataset.extract_both)."""
+    (PCMDataset.extract_both); with ``lpc = n`` the n LPC cepstra per frame and their 2 n statistics behind
+    those."""
     ds = PCMDataset(data_dir or config.DATA_DIR)
     X_stat, y, X_seq, lengths = ds.extract_both(frame_length or config.FRAME_LENGTH,
                                                 frame_shift or config.FRAME_SHIFT, window_type,
                                                 do_endpoint_detection=True, use_only_energy_zcr=True, pitch=pitch,
-                                                sample_rate=config.SAMPLE_RATE)
+                                                sample_rate=config.SAMPLE_RATE, lpc=lpc)
     return X_stat, X_seq, y, lengths
 
 
 def compare(data_dir=None, classifiers=None, test_size=0.2, random_state=42, dtw=False, dtw_template=False,
-            hmm=False, pitch=False):
+            hmm=False, pitch=False, lpc=0):
     """:124-214: each classifier on both feature sets, the reference's split and normalisation
     -> {classifier: {'statistical': acc, 'sequence': acc, 'diff': sequence - statistical}}.
     KNN on the flattened sequences (2 x max_frames columns) runs on the device like the 15-d
@@ -56,9 +57,17 @@ def compare(data_dir=None, classifiers=None, test_size=0.2, random_state=42, dtw
     hmm=True (an extension) adds the row 'HMM' beside them: the same, for one left-to-right Gaussian
     HMM per class (src.models.HmmClassifier, its defaults).
     pitch=True (an extension): every row runs on the 20-d matrix (the 15 columns plus five f0 statistics)
-    and on the (E, ZCR, f0) sequences of the exact autocorrelation pitch track (src.pipeline.PitchTracker)."""
+    and on the (E, ZCR, f0) sequences of the exact autocorrelation pitch track (src.pipeline.PitchTracker).
+    lpc=n (an extension): the n LPC cepstra of every frame join the sequences and their means and standard
+    deviations the matrix (src.pipeline.LpcAnalyzer).  The DTW and HMM kernels take at most 8 channels, so
+    with one of their rows asked for, a sequence width 2 + pitch + n above 8 raises ValueError up front."""
     from sklearn.model_selection import train_test_split
-    X_stat, X_seq, y, lengths = load_both_methods(data_dir, pitch=pitch)
+    if isinstance(lpc, bool) or int(lpc) != lpc or not 0 <= lpc <= 64:
+        raise ValueError("lpc is the number of cepstra per frame, 0 .. 64")
+    if (dtw or dtw_template or hmm) and 2 + bool(pitch) + lpc > 8:
+        raise ValueError("the DTW and HMM rows take sequences of at most 8 channels: E, ZCR%s and %d cepstra are %d"
+                         % (", f0" if pitch else "", lpc, 2 + bool(pitch) + lpc))
+    X_stat, X_seq, y, lengths = load_both_methods(data_dir, pitch=pitch, lpc=lpc)
     X_flat = X_seq.reshape(len(X_seq), -1)
     Xs_tr, Xs_te, y_tr, y_te = train_test_split(X_stat, y, test_size=test_size, random_state=random_state,
                                                 stratify=y)

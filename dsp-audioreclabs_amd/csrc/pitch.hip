@@ -22,16 +22,14 @@
 #include <cstdint>
 
 #include "dsp_audiorec.h"
+#include "pitch_internal.h"
 
 namespace dsp {
 
-constexpr int PITCH_WAVES = 4;
 constexpr int PITCH_LMAX = 4096;
 constexpr int PITCH_HEAD = 16;   // zero bytes in front of a plane: A reads up to 15 bytes before a step
 constexpr int PITCH_TAIL = 336;  // bytes behind sample L - 1: a kept step's B reads at most 303 past it
 constexpr int PITCH_TILES = 3;   // lag tiles that share one A fragment (36 accumulator registers)
-
-typedef int pitch_v4i __attribute__((ext_vector_type(4)));
 
 static inline int pitch_plane_bytes(int L) { return (PITCH_HEAD + L + PITCH_TAIL + 15) & ~15; }
 
@@ -41,12 +39,6 @@ static bool pitch_in_plan(int B, int64_t max_len, int L, int S, int lag_min, int
            lag_max <= L - 1;
 }
 
-__device__ __forceinline__ long long pitch_wave_sum(long long v)
-{
-    for (int m = 32; m; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
 // the larger value, the smaller lag among equals
 __device__ __forceinline__ void pitch_better(long long &bv, int &bl, long long v, int l)
 {
@@ -54,19 +46,6 @@ __device__ __forceinline__ void pitch_better(long long &bv, int &bl, long long v
         bv = v;
         bl = l;
     }
-}
-
-// sixteen bytes from byte address a of a plane (a >= 1, any alignment) as an MFMA operand
-__device__ __forceinline__ pitch_v4i pitch_load_shifted(const unsigned char *plane, int a)
-{
-    const uint32_t *p = (const uint32_t *)(plane + (a & ~3));
-    uint32_t w[5];
-#pragma unroll
-    for (int q = 0; q < 5; q++) w[q] = p[q];
-    pitch_v4i r;
-#pragma unroll
-    for (int q = 0; q < 4; q++) r[q] = (int)__builtin_amdgcn_alignbyte(w[q + 1], w[q], (uint32_t)(a & 3));
-    return r;
 }
 
 // one step of 64 samples for NT lag tiles: A at byte a - col of the planes (shared by the tiles), tile u's
@@ -117,31 +96,7 @@ __global__ __launch_bounds__(PITCH_WAVES * 64) void pitch_track(
     const int16_t *x = pcm + off;
     const int64_t total = offsets[gridDim.x];  // pcm holds at least this many samples
 
-    // c = floor((2 sum + N) / (2 N))
-    // (the sum reads the whole clip once: 16-byte loads between the clip's first and last 16-byte
-    // boundary, single samples in front of and behind them -- nothing outside the clip)
-    const int64_t head = std::min<int64_t>(N, (int64_t)((16 - ((uintptr_t)x & 15)) & 15) / 2);
-    const int64_t nvec = (N - head) / 8;
-    const pitch_v4i *xv = (const pitch_v4i *)(x + head);
-    long long s = 0;
-    if (tid < head) s += x[tid];
-    for (int64_t i = tid; i < nvec; i += PITCH_WAVES * 64) {
-        const pitch_v4i v = xv[i];
-        int part = 0;  // eight int16: no overflow
-#pragma unroll
-        for (int q = 0; q < 4; q++) part += (int)(int16_t)(v[q] & 0xffff) + (v[q] >> 16);
-        s += part;
-    }
-    for (int64_t i = head + nvec * 8 + tid; i < N; i += PITCH_WAVES * 64) s += x[i];
-    s = pitch_wave_sum(s);
-    if (lane == 0) red[wv] = s;
-    __syncthreads();
-    s = 0;
-    for (int q = 0; q < PITCH_WAVES; q++) s += red[q];
-    const long long num = 2 * s + N, den = 2 * N;
-    long long cq = num / den;
-    if (num % den != 0 && num < 0) cq--;
-    const int c = (int)cq;
+    const int c = pitch_clip_centre(x, N, tid, red);  // floor((2 sum + N) / (2 N))
 
     unsigned char *lo = pitch_lds + (size_t)wv * 2 * plane, *hi = lo + plane;
     if (lane < PITCH_HEAD / 4) {
@@ -159,29 +114,12 @@ __global__ __launch_bounds__(PITCH_WAVES * 64) void pitch_track(
         const int16_t *f = x + fs;
         long long e0 = 0;
         bool wide = false;
-        // eight samples per lane and round: as 32-bit words of pcm (funnelled by one sample when the
-        // frame starts on an odd one) where all eight are valid and the word behind them lies inside
-        // pcm, one by one at the frame's end
+        // eight samples per lane and round (pitch_frame_load8)
         const int64_t e_first = off + fs;
         const int odd = (int)(e_first & 1);
         for (int i8 = lane * 8; i8 < img; i8 += 512) {
             int y[8];
-            if (i8 + 8 <= n && e_first + i8 + 8 < total) {
-                const uint32_t *q = (const uint32_t *)pcm + ((e_first + i8 - odd) >> 1);
-                uint32_t w[5];
-#pragma unroll
-                for (int k = 0; k < 4; k++) w[k] = q[k];
-                w[4] = odd ? q[4] : 0u;
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    const uint32_t d = (uint32_t)((((uint64_t)w[k + 1] << 32) | w[k]) >> (16 * odd));
-                    y[2 * k] = (int)(int16_t)(d & 0xffffu) - c;
-                    y[2 * k + 1] = ((int)d >> 16) - c;
-                }
-            } else {
-#pragma unroll
-                for (int k = 0; k < 8; k++) y[k] = i8 + k < n ? (int)f[i8 + k] - c : 0;
-            }
+            pitch_frame_load8(pcm, f, e_first, odd, i8, n, total, c, y);
             uint32_t pl[2] = {0u, 0u}, ph[2] = {0u, 0u};
 #pragma unroll
             for (int k = 0; k < 8; k++) {

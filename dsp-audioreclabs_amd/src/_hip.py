@@ -40,7 +40,8 @@ EXPORTS = ("dsp_extract_lds_bytes", "dsp_extract_fast_layout", "dsp_extract_feat
            "dsp_tree_lds_nodes", "dsp_tree_predict", "dsp_dtw_workspace_bytes", "dsp_dtw_pairwise",
            "dsp_dtw_knn", "dsp_dtw_align_workspace_bytes", "dsp_dtw_align", "dsp_dtw_dba_update",
            "dsp_hmm_workspace_bytes", "dsp_hmm_score", "dsp_hmm_align", "dsp_hmm_accumulate",
-           "dsp_pitch_workspace_bytes", "dsp_pitch_track")
+           "dsp_pitch_workspace_bytes", "dsp_pitch_track", "dsp_lpc_workspace_bytes", "dsp_lpc_autocorr",
+           "dsp_lpc_solve")
 DSP_WAV_OTHER, DSP_WAV_S16_MONO, DSP_WAV_U8_MONO = 0, 1, 2
 
 _lib = None
@@ -172,6 +173,13 @@ def load_library(path=LIB_PATH):
         L.dsp_pitch_workspace_bytes.argtypes = [i32, i64, i32, i32, i32, i32]
         L.dsp_pitch_track.restype = i32
         L.dsp_pitch_track.argtypes = [vp, vp, i32, i64, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, sz, vp]
+    if hasattr(L, "dsp_lpc_autocorr"):  # (older A/B variants lack the LPC analysis)
+        L.dsp_lpc_workspace_bytes.restype = sz
+        L.dsp_lpc_workspace_bytes.argtypes = [i32, i64, i32, i32, i32]
+        L.dsp_lpc_autocorr.restype = i32
+        L.dsp_lpc_autocorr.argtypes = [vp, vp, i32, i64, i32, i32, i32, vp, vp, vp, vp, i32, vp, i32, vp, sz, vp]
+        L.dsp_lpc_solve.restype = i32
+        L.dsp_lpc_solve.argtypes = [vp, i64, i32, i32, vp, vp, vp, vp, vp, vp]
     _lib = L
     return L
 

@@ -20,7 +20,7 @@ from glob import glob
 import numpy as np
 
 from .audio_processing import load_wav_pcm
-from .pipeline import FeatureExtractor, PitchTracker, f0_statistics
+from .pipeline import FeatureExtractor, LpcAnalyzer, PitchTracker, f0_statistics, lpcc_statistics
 
 
 def list_dataset(data_dir):
@@ -221,7 +221,7 @@ class PCMDataset:
 
     def extract_both(self, frame_length, frame_shift, window_type='hamming', do_endpoint_detection=True,
                      use_only_energy_zcr=True, energy_high_ratio=0.5, energy_low_ratio=0.1,
-                     zcr_threshold_ratio=1.5, pitch=False, sample_rate=44100):
+                     zcr_threshold_ratio=1.5, pitch=False, sample_rate=44100, lpc=0):
         """compare_feature_methods.py:43-115 in one fused launch: the statistical matrix and the
         padded sequence tensor of the same clips.
 
@@ -231,26 +231,40 @@ class PCMDataset:
         f0 over the clip's voiced frames (0.0 for a clip without one).  A dataset with 16-bit stereo
         clips held as int32 channel sums raises ValueError then: the track takes int16 samples.
 
-        -> (X_stat float64 [n_ok, 15], y [n_ok], X_seq float64 [n_ok, max_frames, 2|3], lengths
-        [n_ok]).  The kernel writes each clip's per-frame (E, M, ZCR) rows into a zeroed
-        [B, ld, 3] buffer, so cutting it at the batch's longest sequence is exactly
+        ``lpc=n`` (n >= 1) adds the LPC cepstra c_1 .. c_n of every frame (``LpcAnalyzer``, order
+        max(n, 12), the Q15 table of ``window_type``): X_seq gains them as its last n columns (behind f0
+        with ``pitch=True``; 0.0 in the padding) and X_stat gains 2 n columns behind the f0 ones, the
+        mean then the standard deviation of each cepstrum over the clip's frames.  int32 parts raise
+        ValueError as for the pitch track.
+
+        -> (X_stat float64 [n_ok, 15 (+ 5) (+ 2 n)], y [n_ok], X_seq float64 [n_ok, max_frames,
+        2|3 (+ 1) (+ n)], lengths [n_ok]).  The kernel writes each clip's per-frame (E, M, ZCR) rows
+        into a zeroed [B, ld, 3] buffer, so cutting it at the batch's longest sequence is exactly
         ``pad_or_truncate_sequence(seq, max(lengths))`` (fe.py:135-154) for every clip; the
         columns are (E, ZCR) with ``use_only_energy_zcr`` (fe.py:124-128)."""
+        if isinstance(lpc, bool) or int(lpc) != lpc or not 0 <= lpc <= 64:
+            raise ValueError("lpc is the number of cepstra per frame, 0 .. 64")
+        lpc = int(lpc)
         fx = FeatureExtractor(frame_length, frame_shift, window_type, do_endpoint_detection,
                               energy_high_ratio, energy_low_ratio, zcr_threshold_ratio,
                               return_sequences=True, device=self.device)
         run = fx
-        if pitch:
+        if pitch or lpc:
             import torch
             if any(dp.dtype != torch.int16 for _, dp, _, _ in self.parts):
-                raise ValueError("extract_both(pitch=True): the pitch track takes int16 samples, and this dataset "
-                                 "holds 16-bit stereo clips as int32 channel sums")
-            tracker = PitchTracker(frame_length, frame_shift, sample_rate, device=self.device)
+                raise ValueError("extract_both(pitch=True / lpc=n): the pitch track and the LPC analysis take int16 "
+                                 "samples, and this dataset holds 16-bit stereo clips as int32 channel sums")
+            tracker = PitchTracker(frame_length, frame_shift, sample_rate, device=self.device) if pitch else None
+            analyzer = LpcAnalyzer(frame_length, frame_shift, max(lpc, 12), lpc, window_type,
+                                   device=self.device) if lpc else None
 
             def run(dp, do, max_len):
                 o = dict(fx(dp, do, max_len=max_len))
-                track = tracker(dp, o, do, max_len=max_len)
-                o.update(f0=track["f0"], voiced=track["voiced"])
+                if tracker is not None:
+                    track = tracker(dp, o, do, max_len=max_len)
+                    o.update(f0=track["f0"], voiced=track["voiced"])
+                if analyzer is not None:
+                    o.update(cep=analyzer(dp, o, do, max_len=max_len)["cep"])
                 return o
         out = self._run(run)
         ok = (out["status"] & 0xFF) == 0
@@ -263,6 +277,10 @@ class PCMDataset:
             f0, voiced = out["f0"][ok][:, :width], out["voiced"][ok][:, :width]
             seq = np.concatenate([seq, f0[:, :, None]], axis=2)
             feat = np.concatenate([feat, f0_statistics(f0, voiced)], axis=1)
+        if lpc:
+            cep = out["cep"][ok][:, :width]
+            seq = np.concatenate([seq, cep], axis=2)
+            feat = np.concatenate([feat, lpcc_statistics(cep, lengths)], axis=1)
         return feat, self.labels[ok], seq, lengths
 
     def sweep(self, configs, **kw):

@@ -756,6 +756,117 @@ def f0_statistics(f0, voiced):
     return out
 
 
+def lpc_window(window_type, L):
+    """The Q15 table of ``dsp_lpc_autocorr``: floor(w * 32768 + 0.5) of ``create_window``'s fp64 window as
+    int32 [L] (32768 = 1.0); None for the rectangular window (the kernel then takes the frame as it is)."""
+    if window_type == "rectangular":
+        return None
+    return np.floor(create_window(window_type, int(L)) * 32768.0 + 0.5).astype(np.int32)
+
+
+class LpcAnalyzer:
+    """Launch plan for ``dsp_lpc_autocorr`` + ``dsp_lpc_solve`` (csrc/lpc.hip): the exact
+    integer autocorrelation r(0..order) of every Q15-windowed crop frame, then the Levinson-Durbin
+    recursion and ``n_cep`` LPC cepstra in bit-defined fp64.  It runs after a ``FeatureExtractor`` call, on
+    that call's device outputs, like ``PitchTracker``.  The arguments are validated here, without a device."""
+
+    def __init__(self, frame_length, frame_shift, order=12, n_cep=12, window_type='hamming', device=None):
+        for name, v in (("frame_length", frame_length), ("frame_shift", frame_shift), ("order", order),
+                        ("n_cep", n_cep)):
+            if isinstance(v, bool) or int(v) != v:
+                raise ValueError("%s must be an integer" % name)
+        self.L, self.S, self.p, self.Q = int(frame_length), int(frame_shift), int(order), int(n_cep)
+        if not 2 <= self.L <= 4096:
+            raise ValueError("frame_length must be in 2 .. 4096")
+        if self.S < 1:
+            raise ValueError("frame_shift must be positive")
+        if not 1 <= self.p <= min(32, self.L - 1):
+            raise ValueError("order must be in 1 .. min(32, frame_length - 1)")
+        if not 0 <= self.Q <= 64:
+            raise ValueError("n_cep must be in 0 .. 64")
+        self.window_type = window_type
+        self.table = lpc_window(window_type, self.L)  # raises ValueError for an unknown window
+        self.device = device
+        self._ws = self._table_dev = None
+
+    def frames(self, max_len):
+        """Width of the per-frame outputs for clips of up to max_len samples (the widest crop)."""
+        return 1 if max_len <= self.L else (int(max_len) - self.L + self.S - 1) // self.S + 1
+
+    def __call__(self, pcm, extracted, offsets=None, max_len=None):
+        """pcm, offsets: what the ``FeatureExtractor`` call was given (int16); ``extracted``: the dict
+        it returned.  -> dict of device tensors with ld = frames(max_len): r int64 [B, ld, order + 1],
+        a and k float64 [B, ld, order], err float64 and reached int32 [B, ld], cep float64 [B, ld, n_cep];
+        zeros behind a clip's frames and in the rows of failed clips (the solve runs on all B ld rows,
+        and a zero row solves to zeros)."""
+        import torch
+        if str(getattr(pcm, "dtype", "")) not in ("int16", "torch.int16"):
+            raise ValueError("the LPC analysis takes int16 samples (16-bit stereo channel sums in int32 are not supported)")
+        if self.device is None:
+            self.device = _hip.require_device()
+        d = self.device
+        pcm = _as_device(pcm, torch.int16, d)
+        if offsets is None:
+            if pcm.dim() != 2:
+                raise ValueError("1-D packed pcm needs offsets")
+            B, N = pcm.shape
+            off = torch.arange(B + 1, dtype=torch.int64, device=d) * N
+            true_max = N
+        else:
+            off = _as_device(offsets, torch.int64, d)
+            B = off.numel() - 1
+            true_max = None
+        if max_len is None:
+            max_len = true_max if true_max is not None else (int(torch.max(off[1:] - off[:-1]).item()) if B > 0 else 1)
+        max_len = max(int(max_len), 1)
+        rows = extracted["rows"]
+        if rows.shape != (B, _hip.OUT_ROW_WORDS) or rows.dtype != torch.int32 or not rows.is_contiguous():
+            raise ValueError("extracted['rows'] must be the [B, 19] int32 rows of the same batch")
+        ld, p, Q = self.frames(max_len), self.p, self.Q
+        r = torch.zeros((B, ld, p + 1), dtype=torch.int64, device=d)
+        a = torch.empty((B, ld, p), dtype=torch.float64, device=d)
+        k = torch.empty((B, ld, p), dtype=torch.float64, device=d)
+        err = torch.empty((B, ld), dtype=torch.float64, device=d)
+        reached = torch.empty((B, ld), dtype=torch.int32, device=d)
+        cep = torch.empty((B, ld, Q), dtype=torch.float64, device=d)
+        lib = _hip.lib()
+        nbytes = lib.dsp_lpc_workspace_bytes(B, max_len, self.L, self.S, p)
+        if nbytes == 0:
+            raise ValueError("outside the LPC plan")
+        if self._ws is None or self._ws.numel() < nbytes:
+            self._ws = torch.zeros(nbytes, dtype=torch.uint8, device=d)
+        if self.table is not None and self._table_dev is None:
+            self._table_dev = torch.as_tensor(self.table).to(d)
+        rc = lib.dsp_lpc_autocorr(_hip.ptr(pcm.reshape(-1)), _hip.ptr(off), B, max_len, self.L, self.S, p,
+                                  _hip.ptr(self._table_dev), _hip.ptr(rows[:, 15:]), _hip.ptr(rows[:, 17:]),
+                                  _hip.ptr(rows[:, 18:]), _hip.OUT_ROW_WORDS, _hip.ptr(r), ld, _hip.ptr(self._ws),
+                                  self._ws.numel(), _hip.stream_handle(d))
+        _hip.check(rc, "dsp_lpc_autocorr")
+        rc = lib.dsp_lpc_solve(_hip.ptr(r), B * ld, p, Q, _hip.ptr(a), _hip.ptr(k), _hip.ptr(err), _hip.ptr(reached),
+                               _hip.ptr(cep) if Q else None, _hip.stream_handle(d))
+        _hip.check(rc, "dsp_lpc_solve")
+        return dict(r=r, a=a, k=k, err=err, reached=reached, cep=cep)
+
+    def plain_frames(self):
+        """Frames of the last call that took a plain fallback path (one host sync); always 0, the lag sums
+        have none."""
+        import torch
+        return int(self._ws[:4].view(torch.int32).item())
+
+
+def lpcc_statistics(cep, lengths):
+    """mean then std of each cepstrum over each clip's first ``lengths[i]`` frames (numpy, fp64) ->
+    [n, 2 Q]; zeros for a clip without a frame."""
+    cep, lengths = np.asarray(cep, np.float64), np.asarray(lengths).astype(np.int64).reshape(-1)
+    Q = cep.shape[2]
+    out = np.zeros((cep.shape[0], 2 * Q))
+    for i in range(cep.shape[0]):
+        v = cep[i, :max(int(lengths[i]), 0)]
+        if len(v):
+            out[i, :Q], out[i, Q:] = np.mean(v, axis=0), np.std(v, axis=0)
+    return out
+
+
 class SvcIndex:
     """A fitted ``sklearn.svm.SVC(kernel='rbf')`` uploaded once for ``dsp_svc_predict``
     (csrc/svm.hip): libsvm's own arrays -- support_vectors_, _n_support, _dual_coef_, _intercept_,

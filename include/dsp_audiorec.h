@@ -36,7 +36,7 @@ extern "C" {
                               5: queue_ws is 4 KiB (each counter on its own 256-B line);
                               6: the extraction entry points take out_stride (packed result rows);
                                  dsp_knn_classify takes flags (DSP_KNN_REF_READY).
-                              Still 6 with the dsp_mlp_*, dsp_svc_*, dsp_gnb_*, dsp_tree_* and dsp_dtw_* (dsp_dtw_align, dsp_dtw_dba_update included) and dsp_hmm_* and dsp_pitch_* entry points: new symbols only, no
+                              Still 6 with the dsp_mlp_*, dsp_svc_*, dsp_gnb_*, dsp_tree_* and dsp_dtw_* (dsp_dtw_align, dsp_dtw_dba_update included) and dsp_hmm_* and dsp_pitch_* and dsp_lpc_* entry points: new symbols only, no
                               existing signature or meaning changed, so callers built against 6 keep
                               working (a binding that needs them checks for the symbols) */
 
@@ -618,6 +618,61 @@ int dsp_pitch_track(const int16_t *pcm, const int64_t *offsets, int B, int64_t m
                     int frame_shift, int lag_min, int lag_max, const int32_t *start_end,
                     const int32_t *n_frames, const int32_t *status, int out_stride, int32_t *lag, int64_t *peak,
                     int64_t *r0, int ld, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Linear prediction of the crop frames -- the exact integer autocorrelation of each (windowed) frame,
+ * then the Levinson-Durbin recursion and the LPC cepstrum in bit-defined fp64.  csrc/lpc.hip, DESIGN.md
+ * §4.12.  Two entry points: dsp_lpc_autocorr (PCM -> r) and dsp_lpc_solve (r -> a, k, err, cepstrum).
+ *
+ * dsp_lpc_autocorr.  A clip, its crop [st, en), nf, L, S, the centring value c, y = x - c and the frames
+ * f_t[i] are exactly dsp_pitch_track's (above).  p = order, 1 <= p <= min(32, L - 1).
+ *   window    w[i] = min(max(window[i], 0), 32768)                       a Q15 table, 32768 = 1.0
+ *             z_t[i] = (f_t[i] * w[i] + 16384) >> 15                      arithmetic shift (a floor):
+ *             the product rounded half up back to an integer, |z| <= |y| <= 65535.  window == NULL means
+ *             z = f, the same as every entry being 32768.
+ *   r_t(tau)  = sum_{i=0}^{L-1-tau} z_t[i] z_t[i + tau],  tau = 0 .. p     exact int64, |r| < 2^45
+ * r  int64 [B, ld, p + 1].  Frames t >= min(nf, ld) are left untouched, and so are the rows of clips with
+ *             status & 0xFF != 0, of clips longer than max_len and of clips whose crop does not lie inside
+ *             the clip (nothing is read outside a clip).
+ * window      device, int32 [L], or NULL.
+ * pcm, offsets, start_end, n_frames, status, out_stride, ld  as dsp_pitch_track.
+ * workspace   device scratch of dsp_lpc_workspace_bytes(...) bytes (0: outside the plan -- B >= 0,
+ *             max_len >= 1, 2 <= L <= 4096, S >= 1, 1 <= p <= min(32, L - 1)); its first int32 is left
+ *             holding the number of frames answered by a plain fallback path, which is always 0: the lag
+ *             sums run on the vector ALU for every frame and have no fallback.
+ * Host checks before the launch (DSP_ERR_ARGS, DSP_ERR_WORKSPACE); B = 0 returns DSP_OK without a
+ * launch; stream-ordered, no allocation, no copy, no synchronisation.
+ *
+ * dsp_lpc_solve.  r [n, p + 1] int64 (any values, a caller's own included), 1 <= p <= 32, 0 <= n < 2^31,
+ * Q = n_cep, 0 <= Q <= 64.  Every operation below is one IEEE fp64 operation rounded to nearest even, in
+ * this order, never fused; there is no log, exp or sqrt: convert, add, subtract, multiply, divide, compare.
+ *   R[j] = (double) r[j]                      (round to nearest even; exact for |r| < 2^53)
+ *   a[1..p] = k[1..p] = 0;  E = R[0];  m = 0
+ *   for i = 1..p:
+ *       if not (E > 0): stop
+ *       acc = R[i];  for j = 1..i-1 ascending:  acc = acc - a[j] * R[i-j]
+ *       ki = acc / E
+ *       if not (|ki| < 1): stop               (also catches inf; no NaN can arise before it)
+ *       for j = 1..i-1:  a'[j] = a[j] - ki * a[i-j];   a'[i] = ki;   a = a';   k[i] = ki
+ *       E = E * (1 - ki * ki);   m = i
+ *   err = E;  reached = m                     (the predictor is x^[n] = sum_j a_j x[n-j]; a_j = 0 for j > m)
+ *   for n = 1..Q:
+ *       s = 0;  for q = max(1, n-p) .. n-1 ascending:  s = s + ((double) q * c[q]) * a[n-q]
+ *       c[n] = (n <= p ? a[n] : 0) + s / (double) n
+ * With |ki| < 1 enforced every quantity stays finite: no output ever holds a NaN.  An all-zero row gives
+ * reached = 0, err = 0 and zeros everywhere.  c[0] needs a logarithm and is the caller's.
+ * a, k  fp64 [n, p] (a[row][j-1] = a_j);  err fp64 [n];  reached int32 [n];  cep fp64 [n, Q] (c_1 first),
+ *             NULL exactly when Q = 0 is allowed (a NULL cep with Q > 0 is DSP_ERR_ARGS).
+ * Host checks before the launch (DSP_ERR_ARGS); n = 0 returns DSP_OK without a launch; stream-ordered, no
+ * allocation, no copy, no synchronisation, no workspace.
+ */
+size_t dsp_lpc_workspace_bytes(int B, int64_t max_len, int frame_length, int frame_shift, int order);
+int dsp_lpc_autocorr(const int16_t *pcm, const int64_t *offsets, int B, int64_t max_len, int frame_length,
+                     int frame_shift, int order, const int32_t *window, const int32_t *start_end,
+                     const int32_t *n_frames, const int32_t *status, int out_stride, int64_t *r, int ld,
+                     void *workspace, size_t workspace_bytes, void *stream);
+int dsp_lpc_solve(const int64_t *r, int64_t n, int order, int n_cep, double *a, double *k, double *err,
+                  int32_t *reached, double *cep, void *stream);
 
 /*
  * Batch WAV reader -- host only (no GPU, no stream): the file side of load_wav
