@@ -31,15 +31,11 @@
 //   lags    on the vector ALU.  A lane takes four consecutive samples i .. i+3 per round and reads
 //           z[i .. i+3+PM] as 16-byte LDS loads: 4 (PM + 1) multiply-adds on 4 + PM values held in
 //           registers, lag tau in its own int64 accumulator (v_mad_i64_i32).
-//           (-DLPC_ACC_FP64 builds the same kernel with fp64 accumulators and v_fma_f64, which is exact
-//           too -- every operand is an integer below 2^17 and every partial sum an integer below 2^45 --
-//           and measured 4 % slower: the A/B of tools/lpc_bench.py.)
 //   reduce  sixteen lags at a time through the image: lane (tau, q) adds the sixteen lanes 4 j + q of
 //           lag tau, two cross-lane adds finish it, and the lanes with q = 0 write r as int64.
 // No digits, no matrix cores and so no frame that needs a fallback: the workspace's counter is 0.
-// (-DLPC_MFMA builds the other form, pitch.hip's byte digits on the i8 matrix cores with one lag tile: 1 to
-// 4 % faster on clips without a full-scale sample, 12 x slower on clipped ones, whose frames take its plain
-// path -- DESIGN.md §4.12.  It lives behind the macro for the A/B only.)
+// (The forms that were measured against this one and dropped -- fp64 accumulators, the i8 matrix cores --
+// are in DESIGN.md §4.12.)
 //
 // lpc_solve: a thread per row, a and the cepstrum in LDS columns (one per thread, so the triangular
 // loops index LDS and no private array), R converted from the row of r at every use.
@@ -49,7 +45,7 @@
 #include <cstdint>
 
 #include "dsp_audiorec.h"
-#include "pitch_internal.h"
+#include "crop_frames.h"
 
 namespace dsp {
 
@@ -59,16 +55,6 @@ constexpr int LPC_QMAX = 64;
 constexpr int LPC_RED_STRIDE = 68;  // accumulators per lag row of the reduction: 64 + 4, so that the rows
                                     // of the sixteen lags of a pass start four 8-byte banks apart
 constexpr int LPC_SOLVE_THREADS = 64;
-
-#ifdef LPC_ACC_FP64
-typedef double lpc_acc;
-typedef double lpc_op;
-__device__ __forceinline__ void lpc_mad(double &acc, double a, double b) { acc = __builtin_fma(a, b, acc); }
-#else
-typedef long long lpc_acc;
-typedef int lpc_op;
-__device__ __forceinline__ void lpc_mad(long long &acc, int a, int b) { acc += (long long)a * b; }
-#endif
 
 static bool lpc_in_plan(int B, int64_t max_len, int L, int S, int p)
 {
@@ -83,224 +69,89 @@ static int lpc_order_class(int p) { return p <= 16 ? (p + 3) & ~3 : (p <= 24 ? 2
 static int lpc_image_len(int L, int PM) { return (L + 3 + PM + 7) & ~7; }
 static size_t lpc_region_bytes(int L, int PM)
 {
-    return std::max<size_t>((size_t)lpc_image_len(L, PM) * 4, (size_t)16 * LPC_RED_STRIDE * sizeof(lpc_acc));
+    return std::max<size_t>((size_t)lpc_image_len(L, PM) * 4, (size_t)16 * LPC_RED_STRIDE * sizeof(long long));
 }
 
 template <int PM>
-__global__ __launch_bounds__(PITCH_WAVES * 64) void lpc_autocorr(
+__global__ __launch_bounds__(CROP_WAVES * 64) void lpc_autocorr(
     const int16_t *__restrict__ pcm, const int64_t *__restrict__ offsets, int64_t max_len, int L, int S, int p,
     const int32_t *__restrict__ window, const int32_t *__restrict__ start_end, int se_stride,
     const int32_t *__restrict__ n_frames, const int32_t *__restrict__ status, int row_stride, int64_t *__restrict__ r,
     int ld, int zlen, int region, unsigned *plain_frames)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char lpc_lds[];
-    __shared__ long long red[PITCH_WAVES];
+    __shared__ long long red[CROP_WAVES];
     const int64_t b = blockIdx.x;
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);  // wv: scalar
     if (b == 0 && tid == 0) plain_frames[0] = 0u;
-    if ((status[b * row_stride] & 0xFF) != 0) return;
-    const int64_t off = offsets[b], N = offsets[b + 1] - off;
-    const int64_t st = start_end[b * se_stride], en = start_end[b * se_stride + 1];
-    int nf = n_frames[b * row_stride];
-    if (N < 1 || N > max_len || st < 0 || en < st || en > N || nf < 1) return;  // never read outside the clip
-    if (nf > ld) nf = ld;
-    const int16_t *x = pcm + off;
-    const int64_t total = offsets[gridDim.x];  // pcm holds at least this many samples
+    crop_clip clip;
+    if (!crop_gate(clip, pcm, offsets, max_len, start_end, se_stride, n_frames, status, row_stride, ld)) return;
     // w, clamped, in front of the waves' regions (zlen entries, zeros behind L); the barrier inside
-    // pitch_clip_centre orders it before the first frame
+    // crop_clip_centre orders it before the first frame
     int *wt = (int *)lpc_lds;
     if (window)
-        for (int i = tid; i < zlen; i += PITCH_WAVES * 64) wt[i] = i < L ? std::min(std::max(window[i], 0), 32768) : 0;
-    const int c = pitch_clip_centre(x, N, tid, red);
+        for (int i = tid; i < zlen; i += CROP_WAVES * 64) wt[i] = i < L ? std::min(std::max(window[i], 0), 32768) : 0;
+    const int c = crop_clip_centre(clip.x, clip.N, tid, red);
 
     int *zi = (int *)(lpc_lds + (window ? (size_t)zlen * 4 : 0) + (size_t)wv * region);
-    lpc_acc *rd = (lpc_acc *)zi;  // the reduction's rows, over the image once the lag sums have read it
+    long long *rd = (long long *)zi;  // the reduction's rows, over the image once the lag sums have read it
     const int rt = lane >> 2, rq = lane & 3;
 
-    for (int t = wv; t < nf; t += PITCH_WAVES) {
-        const int64_t fs = st + (int64_t)t * S;
-        const int64_t left = en - fs;
-        const int n = left < 0 ? 0 : (left < L ? (int)left : L);  // valid samples, zeros behind them
-        const int16_t *f = x + fs;
-        const int64_t e_first = off + fs;
-        const int odd = (int)(e_first & 1);
+    for (int t = wv; t < clip.nf; t += CROP_WAVES) {
+        const crop_frame fr = crop_frame_at(clip, t, L, S);
         for (int i8 = lane * 8; i8 < zlen; i8 += 512) {
             int y[8];
-            pitch_frame_load8(pcm, f, e_first, odd, i8, n, total, c, y);  // zeros behind the valid samples
+            // zeros behind the valid samples
+            crop_frame_load8(pcm, fr.f, fr.e_first, fr.odd, i8, fr.n, clip.total, c, y);
             if (window) {
-                const pitch_v4i w0 = *(const pitch_v4i *)(wt + i8), w1 = *(const pitch_v4i *)(wt + i8 + 4);
+                const crop_v4i w0 = *(const crop_v4i *)(wt + i8), w1 = *(const crop_v4i *)(wt + i8 + 4);
                 // |y w + 16384| <= 65535 * 32768 + 16384 < 2^31
 #pragma unroll
                 for (int k = 0; k < 8; k++) y[k] = (y[k] * (k < 4 ? w0[k & 3] : w1[k & 3]) + 16384) >> 15;
             }
-            *(pitch_v4i *)(zi + i8) = pitch_v4i{y[0], y[1], y[2], y[3]};
-            *(pitch_v4i *)(zi + i8 + 4) = pitch_v4i{y[4], y[5], y[6], y[7]};
+            *(crop_v4i *)(zi + i8) = crop_v4i{y[0], y[1], y[2], y[3]};
+            *(crop_v4i *)(zi + i8 + 4) = crop_v4i{y[4], y[5], y[6], y[7]};
         }
-        // the image is this wave's own: its writes are ordered before its reads
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        crop_publish();  // the image is this wave's own
 
-        lpc_acc acc[PM + 1];
+        long long acc[PM + 1];
 #pragma unroll
         for (int tau = 0; tau <= PM; tau++) acc[tau] = 0;
         // i0 <= L - 1, so the last entry read is i0 + 3 + PM < zlen
-        for (int i0 = 4 * lane; i0 < n; i0 += 256) {
-            lpc_op v[4 + PM];
+        for (int i0 = 4 * lane; i0 < fr.n; i0 += 256) {
+            int v[4 + PM];
 #pragma unroll
             for (int q = 0; q < 1 + PM / 4; q++) {
-                const pitch_v4i w = *(const pitch_v4i *)(zi + i0 + 4 * q);
+                const crop_v4i w = *(const crop_v4i *)(zi + i0 + 4 * q);
 #pragma unroll
-                for (int u = 0; u < 4; u++) v[4 * q + u] = (lpc_op)w[u];
+                for (int u = 0; u < 4; u++) v[4 * q + u] = w[u];
             }
 #pragma unroll
             for (int u = 0; u < 4; u++)
 #pragma unroll
-                for (int tau = 0; tau <= PM; tau++) lpc_mad(acc[tau], v[u], v[u + tau]);
+                for (int tau = 0; tau <= PM; tau++) acc[tau] += (long long)v[u] * v[u + tau];
         }
 
         const int64_t o = (b * ld + t) * (int64_t)(p + 1);
 #pragma unroll
         for (int base = 0; base <= PM; base += 16) {
-            // the image (or the last pass's rows) has been read by every lane before it is overwritten
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
+            crop_retire();  // the image (or the last pass's rows) has been read before it is overwritten
 #pragma unroll
             for (int u = 0; u < 16; u++)
                 if (base + u <= PM) rd[u * LPC_RED_STRIDE + lane] = acc[base + u];
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            lpc_acc s = 0;
+            crop_publish();
+            long long s = 0;
             if (base + rt <= PM) {
 #pragma unroll
                 for (int j = 0; j < 16; j++) s += rd[rt * LPC_RED_STRIDE + 4 * j + rq];
             }
             s += __shfl_xor(s, 1, 64);
             s += __shfl_xor(s, 2, 64);
-            if (rq == 0 && base + rt <= p) r[o + base + rt] = (int64_t)s;
+            if (rq == 0 && base + rt <= p) r[o + base + rt] = s;
         }
-        // the next frame's image is written only after this frame's reads
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        crop_retire();  // the next frame's image is written only after this frame's reads
     }
 }
-
-#ifdef LPC_MFMA
-// The other form of the lag sums, built only for the A/B of tools/lpc_bench.py (lib/libdsp_lpc_mfma.so):
-// pitch.hip's scheme with its one lag tile from T = 0.  z is split into balanced byte digits in two LDS byte
-// planes, A[m][k] = z[i0 + k - m], B[k][n] = z[i0 + k + 16 n], so D[m][n] of v_mfma_i32_16x16x64_i8 is lag
-// 16 n + m (n <= 2 is kept), three digit pairs in int32 recombined in int64; a frame with a digit that is no
-// int8 (z >= 32640 or z < -32896) takes one lag per lane in plain int64 and is counted in the workspace.
-constexpr int LPC_HEAD = 16;   // zero bytes in front of a plane: A reads up to 15 bytes before a step
-constexpr int LPC_TAIL = 336;  // bytes behind sample L - 1: a step's B reads at most 303 past it
-static int lpc_plane_bytes(int L) { return (LPC_HEAD + L + LPC_TAIL + 15) & ~15; }
-
-__global__ void lpc_begin(unsigned *counters)
-{
-    counters[0] = 0u;
-}
-
-__global__ __launch_bounds__(PITCH_WAVES * 64) void lpc_autocorr_mfma(
-    const int16_t *__restrict__ pcm, const int64_t *__restrict__ offsets, int64_t max_len, int L, int S, int p,
-    const int32_t *__restrict__ window, const int32_t *__restrict__ start_end, int se_stride,
-    const int32_t *__restrict__ n_frames, const int32_t *__restrict__ status, int row_stride, int64_t *__restrict__ r,
-    int ld, int wlen, int plane, unsigned *plain_frames)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char lpc_lds[];
-    __shared__ long long red[PITCH_WAVES];
-    const int64_t b = blockIdx.x;
-    const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    if ((status[b * row_stride] & 0xFF) != 0) return;
-    const int64_t off = offsets[b], N = offsets[b + 1] - off;
-    const int64_t st = start_end[b * se_stride], en = start_end[b * se_stride + 1];
-    int nf = n_frames[b * row_stride];
-    if (N < 1 || N > max_len || st < 0 || en < st || en > N || nf < 1) return;
-    if (nf > ld) nf = ld;
-    const int16_t *x = pcm + off;
-    const int64_t total = offsets[gridDim.x];
-    int *wt = (int *)lpc_lds;  // wlen = L rounded up to 8 entries
-    if (window)
-        for (int i = tid; i < wlen; i += PITCH_WAVES * 64) wt[i] = i < L ? std::min(std::max(window[i], 0), 32768) : 0;
-    const int c = pitch_clip_centre(x, N, tid, red);
-
-    unsigned char *lo = lpc_lds + (window ? (size_t)wlen * 4 : 0) + (size_t)wv * 2 * plane, *hi = lo + plane;
-    if (lane < LPC_HEAD / 4) {
-        ((uint32_t *)lo)[lane] = 0u;
-        ((uint32_t *)hi)[lane] = 0u;
-    }
-    const int img = plane - LPC_HEAD;  // a multiple of 16
-    const int col = lane & 15, grp = lane >> 4;
-
-    for (int t = wv; t < nf; t += PITCH_WAVES) {
-        const int64_t fs = st + (int64_t)t * S;
-        const int64_t left = en - fs;
-        const int n = left < 0 ? 0 : (left < L ? (int)left : L);
-        const int16_t *f = x + fs;
-        const int64_t e_first = off + fs;
-        const int odd = (int)(e_first & 1);
-        bool wide = false;
-        for (int i8 = lane * 8; i8 < img; i8 += 512) {
-            int y[8];
-            pitch_frame_load8(pcm, f, e_first, odd, i8, n, total, c, y);
-            if (window && i8 < wlen) {  // (behind wlen every y is 0)
-                const pitch_v4i w0 = *(const pitch_v4i *)(wt + i8), w1 = *(const pitch_v4i *)(wt + i8 + 4);
-#pragma unroll
-                for (int k = 0; k < 8; k++) y[k] = (y[k] * (k < 4 ? w0[k & 3] : w1[k & 3]) + 16384) >> 15;
-            }
-            uint32_t pl[2] = {0u, 0u}, ph[2] = {0u, 0u};
-#pragma unroll
-            for (int k = 0; k < 8; k++) {
-                const int dl = ((y[k] + 128) & 255) - 128, dh = (y[k] - dl) >> 8;
-                wide |= dh < -128 || dh > 127;
-                pl[k >> 2] |= (uint32_t)(dl & 255) << (8 * (k & 3));
-                ph[k >> 2] |= (uint32_t)(dh & 255) << (8 * (k & 3));
-            }
-            *(uint2 *)(lo + LPC_HEAD + i8) = make_uint2(pl[0], pl[1]);
-            *(uint2 *)(hi + LPC_HEAD + i8) = make_uint2(ph[0], ph[1]);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-
-        const int64_t o = (b * ld + t) * (int64_t)(p + 1);
-        if (__any(wide)) {
-            if (lane <= p) {
-                long long acc = 0;
-                for (int i = 0; i + lane < n; i++) {
-                    int u = (int)f[i] - c, v = (int)f[i + lane] - c;
-                    if (window) {
-                        u = (u * wt[i] + 16384) >> 15;
-                        v = (v * wt[i + lane] + 16384) >> 15;
-                    }
-                    acc += (long long)u * v;
-                }
-                r[o + lane] = acc;
-            }
-            if (lane == 0) atomicAdd(plain_frames, 1u);
-        } else {
-            pitch_v4i hh = {0, 0, 0, 0}, mid = {0, 0, 0, 0}, ll = {0, 0, 0, 0};
-            const int a0 = LPC_HEAD + 16 * grp, b0 = a0 + 16 * col;
-            for (int i0 = 0; i0 < n; i0 += 64) {
-                const pitch_v4i al = pitch_load_shifted(lo, a0 + i0 - col), ah = pitch_load_shifted(hi, a0 + i0 - col);
-                const pitch_v4i bl = *(const pitch_v4i *)(lo + b0 + i0), bh = *(const pitch_v4i *)(hi + b0 + i0);
-                hh = __builtin_amdgcn_mfma_i32_16x16x64_i8(ah, bh, hh, 0, 0, 0);
-                ll = __builtin_amdgcn_mfma_i32_16x16x64_i8(al, bl, ll, 0, 0, 0);
-                mid = __builtin_amdgcn_mfma_i32_16x16x64_i8(ah, bl, mid, 0, 0, 0);
-                mid = __builtin_amdgcn_mfma_i32_16x16x64_i8(al, bh, mid, 0, 0, 0);
-            }
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                // D[m][n]: n on the lane's low four bits, m = 4 (lane >> 4) + q
-                const int tau = 16 * col + 4 * grp + q;
-                if (tau <= p) r[o + tau] = 65536ll * hh[q] + 256ll * mid[q] + ll[q];
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    }
-}
-#endif  // LPC_MFMA
 
 #pragma clang fp contract(off)
 // a_j at a[j * T], c_q at c[q * T]: this thread's columns of the two LDS tables (row 0 of each unused)
@@ -367,7 +218,7 @@ static hipError_t lpc_launch(int B, size_t lds, hipStream_t s, const int16_t *pc
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(lpc_autocorr<PM>, dim3((unsigned)B), dim3(PITCH_WAVES * 64), lds, s, pcm, offsets, max_len, L, S,
+    hipLaunchKernelGGL(lpc_autocorr<PM>, dim3((unsigned)B), dim3(CROP_WAVES * 64), lds, s, pcm, offsets, max_len, L, S,
                        p, window, start_end, se_stride, n_frames, status, row_stride, r, ld, zlen, region, counter);
     return hipGetLastError();
 }
@@ -385,27 +236,16 @@ extern "C" int dsp_lpc_autocorr(const int16_t *pcm, const int64_t *offsets, int 
                                 void *workspace, size_t workspace_bytes, void *stream)
 {
     if (!dsp::lpc_in_plan(B, max_len, frame_length, frame_shift, order)) return DSP_ERR_ARGS;
-    if (ld < 1 || (out_stride != 0 && out_stride < DSP_OUT_ROW_WORDS)) return DSP_ERR_ARGS;
-    if (B == 0) return DSP_OK;
-    if (!pcm || !offsets || !start_end || !n_frames || !status || !r) return DSP_ERR_ARGS;
-    if (((uintptr_t)pcm & 3) || ((uintptr_t)r & 7) || ((uintptr_t)window & 3)) return DSP_ERR_ARGS;
-    if (!workspace || workspace_bytes < 256) return DSP_ERR_WORKSPACE;
+    const bool outputs_ok = r && !((uintptr_t)r & 7) && !((uintptr_t)window & 3);
+    int se, rs, rc;
+    if (!dsp::crop_host_checks(B, ld, out_stride, pcm, offsets, start_end, n_frames, status, outputs_ok, workspace,
+                               workspace_bytes, &se, &rs, &rc))
+        return rc;
     hipStream_t s = (hipStream_t)stream;
-#ifdef LPC_MFMA
-    const int wlen = (frame_length + 7) & ~7, plane = dsp::lpc_plane_bytes(frame_length);
-    const size_t lds_mfma = (window ? (size_t)wlen * 4 : 0) + (size_t)dsp::PITCH_WAVES * 2 * plane;  // at most 52 KiB
-    hipLaunchKernelGGL(dsp::lpc_begin, dim3(1), dim3(1), 0, s, (unsigned *)workspace);
-    hipLaunchKernelGGL(dsp::lpc_autocorr_mfma, dim3((unsigned)B), dim3(dsp::PITCH_WAVES * 64), lds_mfma, s, pcm, offsets,
-                       max_len, frame_length, frame_shift, order, window, start_end, out_stride ? out_stride : 2, n_frames,
-                       status, out_stride ? out_stride : 1, r, ld, wlen, plane, (unsigned *)workspace);
-    const hipError_t em = hipGetLastError();
-    return em == hipSuccess ? DSP_OK : DSP_ERR_HIP + (int)em;
-#endif
     const int PM = dsp::lpc_order_class(order);
     const int zlen = dsp::lpc_image_len(frame_length, PM);
     const int region = (int)((dsp::lpc_region_bytes(frame_length, PM) + 15) & ~(size_t)15);
-    const size_t lds = (window ? (size_t)zlen * 4 : 0) + (size_t)dsp::PITCH_WAVES * region;  // at most 81 KiB
-    const int se = out_stride ? out_stride : 2, rs = out_stride ? out_stride : 1;
+    const size_t lds = (window ? (size_t)zlen * 4 : 0) + (size_t)dsp::CROP_WAVES * region;  // at most 81 KiB
     hipError_t e;
 #define LPC_CASE(P)                                                                                                   \
     case P:                                                                                                           \

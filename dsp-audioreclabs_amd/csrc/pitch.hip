@@ -22,7 +22,7 @@
 #include <cstdint>
 
 #include "dsp_audiorec.h"
-#include "pitch_internal.h"
+#include "crop_frames.h"
 
 namespace dsp {
 
@@ -48,19 +48,32 @@ __device__ __forceinline__ void pitch_better(long long &bv, int &bl, long long v
     }
 }
 
+// sixteen bytes from byte address a of a plane (a >= 1, any alignment) as an MFMA operand
+__device__ __forceinline__ crop_v4i pitch_load_shifted(const unsigned char *plane, int a)
+{
+    const uint32_t *p = (const uint32_t *)(plane + (a & ~3));
+    uint32_t w[5];
+#pragma unroll
+    for (int q = 0; q < 5; q++) w[q] = p[q];
+    crop_v4i r;
+#pragma unroll
+    for (int q = 0; q < 4; q++) r[q] = (int)__builtin_amdgcn_alignbyte(w[q + 1], w[q], (uint32_t)(a & 3));
+    return r;
+}
+
 // one step of 64 samples for NT lag tiles: A at byte a - col of the planes (shared by the tiles), tile u's
 // B at byte bo + 256 u; every load is issued before the first MFMA
 template <int NT>
 __device__ __forceinline__ void pitch_step(const unsigned char *lo, const unsigned char *hi, int a, int col, int bo,
-                                           pitch_v4i (&hh)[PITCH_TILES], pitch_v4i (&mid)[PITCH_TILES],
-                                           pitch_v4i (&ll)[PITCH_TILES])
+                                           crop_v4i (&hh)[PITCH_TILES], crop_v4i (&mid)[PITCH_TILES],
+                                           crop_v4i (&ll)[PITCH_TILES])
 {
-    const pitch_v4i al = pitch_load_shifted(lo, a - col), ah = pitch_load_shifted(hi, a - col);
-    pitch_v4i bl[NT], bh[NT];
+    const crop_v4i al = pitch_load_shifted(lo, a - col), ah = pitch_load_shifted(hi, a - col);
+    crop_v4i bl[NT], bh[NT];
 #pragma unroll
     for (int u = 0; u < NT; u++) {
-        bl[u] = *(const pitch_v4i *)(lo + bo + 256 * u);
-        bh[u] = *(const pitch_v4i *)(hi + bo + 256 * u);
+        bl[u] = *(const crop_v4i *)(lo + bo + 256 * u);
+        bh[u] = *(const crop_v4i *)(hi + bo + 256 * u);
     }
 #pragma unroll
     for (int u = 0; u < NT; u++) hh[u] = __builtin_amdgcn_mfma_i32_16x16x64_i8(ah, bh[u], hh[u], 0, 0, 0);
@@ -77,26 +90,20 @@ __global__ void pitch_begin(unsigned *counters)
     counters[0] = 0u;
 }
 
-__global__ __launch_bounds__(PITCH_WAVES * 64) void pitch_track(
+__global__ __launch_bounds__(CROP_WAVES * 64) void pitch_track(
     const int16_t *__restrict__ pcm, const int64_t *__restrict__ offsets, int64_t max_len, int L, int S, int lag_min,
     int lag_max, const int32_t *__restrict__ start_end, int se_stride, const int32_t *__restrict__ n_frames,
     const int32_t *__restrict__ status, int row_stride, int32_t *__restrict__ lag, int64_t *__restrict__ peak,
     int64_t *__restrict__ r0, int ld, int plane, unsigned *plain_frames)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char pitch_lds[];
-    __shared__ long long red[PITCH_WAVES];
+    __shared__ long long red[CROP_WAVES];
     const int64_t b = blockIdx.x;
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);  // wv: scalar
-    if ((status[b * row_stride] & 0xFF) != 0) return;
-    const int64_t off = offsets[b], N = offsets[b + 1] - off;
-    const int64_t st = start_end[b * se_stride], en = start_end[b * se_stride + 1];
-    int nf = n_frames[b * row_stride];
-    if (N < 1 || N > max_len || st < 0 || en < st || en > N || nf < 1) return;  // never read outside the clip
-    if (nf > ld) nf = ld;
-    const int16_t *x = pcm + off;
-    const int64_t total = offsets[gridDim.x];  // pcm holds at least this many samples
+    crop_clip clip;
+    if (!crop_gate(clip, pcm, offsets, max_len, start_end, se_stride, n_frames, status, row_stride, ld)) return;
 
-    const int c = pitch_clip_centre(x, N, tid, red);  // floor((2 sum + N) / (2 N))
+    const int c = crop_clip_centre(clip.x, clip.N, tid, red);  // floor((2 sum + N) / (2 N))
 
     unsigned char *lo = pitch_lds + (size_t)wv * 2 * plane, *hi = lo + plane;
     if (lane < PITCH_HEAD / 4) {
@@ -107,19 +114,14 @@ __global__ __launch_bounds__(PITCH_WAVES * 64) void pitch_track(
     const int tau0 = lag_min & ~15, ntile = (lag_max - tau0) / 256 + 1;
     const int col = lane & 15, grp = lane >> 4;
 
-    for (int t = wv; t < nf; t += PITCH_WAVES) {
-        const int64_t fs = st + (int64_t)t * S;
-        const int64_t left = en - fs;
-        const int n = left < 0 ? 0 : (left < L ? (int)left : L);  // valid samples, zeros behind them
-        const int16_t *f = x + fs;
+    for (int t = wv; t < clip.nf; t += CROP_WAVES) {
+        const crop_frame fr = crop_frame_at(clip, t, L, S);
         long long e0 = 0;
         bool wide = false;
-        // eight samples per lane and round (pitch_frame_load8)
-        const int64_t e_first = off + fs;
-        const int odd = (int)(e_first & 1);
+        // eight samples per lane and round (crop_frame_load8)
         for (int i8 = lane * 8; i8 < img; i8 += 512) {
             int y[8];
-            pitch_frame_load8(pcm, f, e_first, odd, i8, n, total, c, y);
+            crop_frame_load8(pcm, fr.f, fr.e_first, fr.odd, i8, fr.n, clip.total, c, y);
             uint32_t pl[2] = {0u, 0u}, ph[2] = {0u, 0u};
 #pragma unroll
             for (int k = 0; k < 8; k++) {
@@ -132,37 +134,35 @@ __global__ __launch_bounds__(PITCH_WAVES * 64) void pitch_track(
             *(uint2 *)(lo + PITCH_HEAD + i8) = make_uint2(pl[0], pl[1]);
             *(uint2 *)(hi + PITCH_HEAD + i8) = make_uint2(ph[0], ph[1]);
         }
-        e0 = pitch_wave_sum(e0);
-        // the image is this wave's own: its writes are ordered before its reads
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        e0 = crop_wave_sum(e0);
+        crop_publish();  // the image is this wave's own
 
         long long bv = INT64_MIN;
         int bl = INT32_MAX;
         if (__any(wide)) {
             for (int tau = lag_min + lane; tau <= lag_max; tau += 64) {
                 long long r = 0;
-                for (int i = 0; i + tau < n; i++) r += (long long)((int)f[i] - c) * (long long)((int)f[i + tau] - c);
+                for (int i = 0; i + tau < fr.n; i++)
+                    r += (long long)((int)fr.f[i] - c) * (long long)((int)fr.f[i + tau] - c);
                 pitch_better(bv, bl, r, tau);
             }
             if (lane == 0) atomicAdd(plain_frames, 1u);
         } else {
             for (int tg = 0; tg < ntile; tg += PITCH_TILES) {
                 const int base = tau0 + 256 * tg;
-                pitch_v4i hh[PITCH_TILES], mid[PITCH_TILES], ll[PITCH_TILES];
+                crop_v4i hh[PITCH_TILES], mid[PITCH_TILES], ll[PITCH_TILES];
 #pragma unroll
-                for (int u = 0; u < PITCH_TILES; u++) hh[u] = mid[u] = ll[u] = pitch_v4i{0, 0, 0, 0};
-                // tile u's steps end where its B starts behind the frame (i0 + base + 256 u >= n), so the
+                for (int u = 0; u < PITCH_TILES; u++) hh[u] = mid[u] = ll[u] = crop_v4i{0, 0, 0, 0};
+                // tile u's steps end where its B starts behind the frame (i0 + base + 256 u >= fr.n), so the
                 // steps run with three tiles first, then two, then one: no condition inside a step
                 const int nt = ntile - tg < PITCH_TILES ? ntile - tg : PITCH_TILES;
                 const int a0 = PITCH_HEAD + 16 * grp, b0 = a0 + base + 16 * col;
                 int i0 = 0;
                 if (nt >= 3)
-                    for (; i0 + base + 512 < n; i0 += 64) pitch_step<3>(lo, hi, a0 + i0, col, b0 + i0, hh, mid, ll);
+                    for (; i0 + base + 512 < fr.n; i0 += 64) pitch_step<3>(lo, hi, a0 + i0, col, b0 + i0, hh, mid, ll);
                 if (nt >= 2)
-                    for (; i0 + base + 256 < n; i0 += 64) pitch_step<2>(lo, hi, a0 + i0, col, b0 + i0, hh, mid, ll);
-                for (; i0 + base < n; i0 += 64) pitch_step<1>(lo, hi, a0 + i0, col, b0 + i0, hh, mid, ll);
+                    for (; i0 + base + 256 < fr.n; i0 += 64) pitch_step<2>(lo, hi, a0 + i0, col, b0 + i0, hh, mid, ll);
+                for (; i0 + base < fr.n; i0 += 64) pitch_step<1>(lo, hi, a0 + i0, col, b0 + i0, hh, mid, ll);
 #pragma unroll
                 for (int u = 0; u < PITCH_TILES; u++) {
                     if (tg + u < ntile) {
@@ -188,9 +188,7 @@ __global__ __launch_bounds__(PITCH_WAVES * 64) void pitch_track(
             peak[o] = bv;
             r0[o] = e0;
         }
-        // the next frame's image is written only after this frame's reads
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        crop_retire();  // the next frame's image is written only after this frame's reads
     }
 }
 
@@ -208,18 +206,18 @@ extern "C" int dsp_pitch_track(const int16_t *pcm, const int64_t *offsets, int B
                                int64_t *peak, int64_t *r0, int ld, void *workspace, size_t workspace_bytes, void *stream)
 {
     if (!dsp::pitch_in_plan(B, max_len, frame_length, frame_shift, lag_min, lag_max)) return DSP_ERR_ARGS;
-    if (ld < 1 || (out_stride != 0 && out_stride < DSP_OUT_ROW_WORDS)) return DSP_ERR_ARGS;
-    if (B == 0) return DSP_OK;
-    if (!pcm || !offsets || !start_end || !n_frames || !status || !lag || !peak || !r0) return DSP_ERR_ARGS;
-    if (((uintptr_t)pcm & 3) || ((uintptr_t)peak & 7) || ((uintptr_t)r0 & 7)) return DSP_ERR_ARGS;
-    if (!workspace || workspace_bytes < 256) return DSP_ERR_WORKSPACE;
+    const bool outputs_ok = lag && peak && r0 && !((uintptr_t)peak & 7) && !((uintptr_t)r0 & 7);
+    int se_stride, row_stride, rc;
+    if (!dsp::crop_host_checks(B, ld, out_stride, pcm, offsets, start_end, n_frames, status, outputs_ok, workspace,
+                               workspace_bytes, &se_stride, &row_stride, &rc))
+        return rc;
     hipStream_t s = (hipStream_t)stream;
     const int plane = dsp::pitch_plane_bytes(frame_length);
-    const size_t lds = (size_t)dsp::PITCH_WAVES * 2 * plane;  // at most 36 KiB
+    const size_t lds = (size_t)dsp::CROP_WAVES * 2 * plane;  // at most 36 KiB
     hipLaunchKernelGGL(dsp::pitch_begin, dim3(1), dim3(1), 0, s, (unsigned *)workspace);
-    hipLaunchKernelGGL(dsp::pitch_track, dim3((unsigned)B), dim3(dsp::PITCH_WAVES * 64), lds, s, pcm, offsets, max_len,
-                       frame_length, frame_shift, lag_min, lag_max, start_end, out_stride ? out_stride : 2, n_frames,
-                       status, out_stride ? out_stride : 1, lag, peak, r0, ld, plane, (unsigned *)workspace);
+    hipLaunchKernelGGL(dsp::pitch_track, dim3((unsigned)B), dim3(dsp::CROP_WAVES * 64), lds, s, pcm, offsets, max_len,
+                       frame_length, frame_shift, lag_min, lag_max, start_end, se_stride, n_frames, status, row_stride,
+                       lag, peak, r0, ld, plane, (unsigned *)workspace);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? DSP_OK : DSP_ERR_HIP + (int)e;
 }

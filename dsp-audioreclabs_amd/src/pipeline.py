@@ -655,35 +655,21 @@ def hmm_uniform_segmentation(lengths, n_states, Smax):
     return np.where((s < S[:, None]) & (n >= S)[:, None], seg, -1).astype(np.int32)
 
 
-class PitchTracker:
-    """Launch plan for ``dsp_pitch_track`` (csrc/pitch.hip, DESIGN.md §4.11): the exact short-time
-    autocorrelation of every crop frame, the smallest lag of its maximum inside
-    [sample_rate // f0_max, sample_rate // f0_min] (clamped to [1, L - 1]), and the voicing decision and
-    f0 derived from them on the device.  It runs after a ``FeatureExtractor`` call, on that call's
-    device outputs.  The arguments are validated here, without a device."""
+class _CropFramePlan:
+    """What the launch plans of the two crop-frame kernels (csrc/crop_frames.h) share: ``PitchTracker`` and
+    ``LpcAnalyzer`` run after a ``FeatureExtractor`` call, on that call's device outputs, and validate
+    their arguments without a device."""
+    _takes = _plan = None  # "the pitch track takes", "the pitch plan": the error texts name the analysis
 
-    def __init__(self, frame_length, frame_shift, sample_rate, f0_min=60.0, f0_max=400.0, voicing=(3, 10),
-                 device=None):
-        for name, v in (("frame_length", frame_length), ("frame_shift", frame_shift), ("sample_rate", sample_rate)):
+    def __init__(self, device, frame_length, frame_shift, **integers):
+        for name, v in dict(frame_length=frame_length, frame_shift=frame_shift, **integers).items():
             if isinstance(v, bool) or int(v) != v:
                 raise ValueError("%s must be an integer" % name)
-        self.L, self.S, self.sample_rate = int(frame_length), int(frame_shift), int(sample_rate)
+        self.L, self.S = int(frame_length), int(frame_shift)
         if not 2 <= self.L <= 4096:
             raise ValueError("frame_length must be in 2 .. 4096")
-        if self.S < 1 or self.sample_rate < 1:
-            raise ValueError("frame_shift and sample_rate must be positive")
-        f0_min, f0_max = float(f0_min), float(f0_max)
-        if not 0.0 < f0_min <= f0_max or not np.isfinite(f0_max):
-            raise ValueError("need 0 < f0_min <= f0_max")
-        try:
-            vnum, vden = voicing
-        except (TypeError, ValueError):
-            raise ValueError("voicing is a pair (vnum, vden)")
-        if any(isinstance(v, bool) or int(v) != v for v in (vnum, vden)) or not 1 <= vnum <= vden <= 1024:
-            raise ValueError("voicing needs integers 1 <= vnum <= vden <= 1024")
-        self.vnum, self.vden = int(vnum), int(vden)
-        self.lag_min = min(max(int(self.sample_rate // f0_max), 1), self.L - 1)
-        self.lag_max = min(max(int(self.sample_rate // f0_min), 1), self.L - 1)
+        if self.S < 1:
+            raise ValueError("frame_shift must be positive")
         self.device = device
         self._ws = None
 
@@ -691,16 +677,15 @@ class PitchTracker:
         """Width of the per-frame outputs for clips of up to max_len samples (the widest crop)."""
         return 1 if max_len <= self.L else (int(max_len) - self.L + self.S - 1) // self.S + 1
 
-    def __call__(self, pcm, extracted, offsets=None, max_len=None):
-        """pcm, offsets: what the ``FeatureExtractor`` call was given (int16); ``extracted``: the dict
-        it returned.  -> dict of device tensors [B, frames(max_len)]: lag int32, peak and r0 int64,
-        voiced bool, f0 float64; zeros (False) behind a clip's frames and in the rows of failed clips."""
+    def _batch(self, pcm, extracted, offsets, max_len):
+        """The batch a call was given (int16 samples: anything else is refused before a device is asked
+        for) -> (pcm_flat, off, B, max_len, rows, ld), tensors on the device."""
         import torch
+        if str(getattr(pcm, "dtype", "")) not in ("int16", "torch.int16"):
+            raise ValueError("%s int16 samples (16-bit stereo channel sums in int32 are not supported)" % self._takes)
         if self.device is None:
             self.device = _hip.require_device()
         d = self.device
-        if str(getattr(pcm, "dtype", "")) not in ("int16", "torch.int16"):
-            raise ValueError("the pitch track takes int16 samples (16-bit stereo channel sums in int32 are not supported)")
         pcm = _as_device(pcm, torch.int16, d)
         if offsets is None:
             if pcm.dim() != 2:
@@ -718,30 +703,72 @@ class PitchTracker:
         rows = extracted["rows"]
         if rows.shape != (B, _hip.OUT_ROW_WORDS) or rows.dtype != torch.int32 or not rows.is_contiguous():
             raise ValueError("extracted['rows'] must be the [B, 19] int32 rows of the same batch")
-        ld = self.frames(max_len)
+        return pcm.reshape(-1), off, B, max_len, rows, self.frames(max_len)
+
+    def _workspace(self, nbytes):
+        """The plan's device workspace, grown to nbytes (0: the library refused the shape)."""
+        import torch
+        if nbytes == 0:
+            raise ValueError("outside %s" % self._plan)
+        if self._ws is None or self._ws.numel() < nbytes:
+            self._ws = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
+        return self._ws
+
+    def plain_frames(self):
+        """Frames of the last call that took a plain int64 fallback path (one host sync); the LPC lag
+        sums have none, so 0 there."""
+        import torch
+        return int(self._ws[:4].view(torch.int32).item())
+
+
+class PitchTracker(_CropFramePlan):
+    """Launch plan for ``dsp_pitch_track`` (csrc/pitch.hip, DESIGN.md §4.11): the exact short-time
+    autocorrelation of every crop frame, the smallest lag of its maximum inside
+    [sample_rate // f0_max, sample_rate // f0_min] (clamped to [1, L - 1]), and the voicing decision and
+    f0 derived from them on the device.  It runs after a ``FeatureExtractor`` call, on that call's
+    device outputs.  The arguments are validated here, without a device."""
+    _takes, _plan = "the pitch track takes", "the pitch plan"
+
+    def __init__(self, frame_length, frame_shift, sample_rate, f0_min=60.0, f0_max=400.0, voicing=(3, 10),
+                 device=None):
+        super().__init__(device, frame_length, frame_shift, sample_rate=sample_rate)
+        self.sample_rate = int(sample_rate)
+        if self.sample_rate < 1:
+            raise ValueError("sample_rate must be positive")
+        f0_min, f0_max = float(f0_min), float(f0_max)
+        if not 0.0 < f0_min <= f0_max or not np.isfinite(f0_max):
+            raise ValueError("need 0 < f0_min <= f0_max")
+        try:
+            vnum, vden = voicing
+        except (TypeError, ValueError):
+            raise ValueError("voicing is a pair (vnum, vden)")
+        if any(isinstance(v, bool) or int(v) != v for v in (vnum, vden)) or not 1 <= vnum <= vden <= 1024:
+            raise ValueError("voicing needs integers 1 <= vnum <= vden <= 1024")
+        self.vnum, self.vden = int(vnum), int(vden)
+        self.lag_min = min(max(int(self.sample_rate // f0_max), 1), self.L - 1)
+        self.lag_max = min(max(int(self.sample_rate // f0_min), 1), self.L - 1)
+
+    def __call__(self, pcm, extracted, offsets=None, max_len=None):
+        """pcm, offsets: what the ``FeatureExtractor`` call was given (int16); ``extracted``: the dict
+        it returned.  -> dict of device tensors [B, frames(max_len)]: lag int32, peak and r0 int64,
+        voiced bool, f0 float64; zeros (False) behind a clip's frames and in the rows of failed clips."""
+        import torch
+        pcm, off, B, max_len, rows, ld = self._batch(pcm, extracted, offsets, max_len)
+        d = self.device
         lag = torch.zeros((B, ld), dtype=torch.int32, device=d)
         peak = torch.zeros((B, ld), dtype=torch.int64, device=d)
         r0 = torch.zeros((B, ld), dtype=torch.int64, device=d)
         lib = _hip.lib()
-        nbytes = lib.dsp_pitch_workspace_bytes(B, max_len, self.L, self.S, self.lag_min, self.lag_max)
-        if nbytes == 0:
-            raise ValueError("outside the pitch plan")
-        if self._ws is None or self._ws.numel() < nbytes:
-            self._ws = torch.zeros(nbytes, dtype=torch.uint8, device=d)
-        rc = lib.dsp_pitch_track(_hip.ptr(pcm.reshape(-1)), _hip.ptr(off), B, max_len, self.L, self.S, self.lag_min,
-                                 self.lag_max, _hip.ptr(rows[:, 15:]), _hip.ptr(rows[:, 17:]), _hip.ptr(rows[:, 18:]),
-                                 _hip.OUT_ROW_WORDS, _hip.ptr(lag), _hip.ptr(peak), _hip.ptr(r0), ld,
-                                 _hip.ptr(self._ws), self._ws.numel(), _hip.stream_handle(d))
+        ws = self._workspace(lib.dsp_pitch_workspace_bytes(B, max_len, self.L, self.S, self.lag_min, self.lag_max))
+        rc = lib.dsp_pitch_track(_hip.ptr(pcm), _hip.ptr(off), B, max_len, self.L, self.S, self.lag_min, self.lag_max,
+                                 _hip.ptr(rows[:, 15:]), _hip.ptr(rows[:, 17:]), _hip.ptr(rows[:, 18:]),
+                                 _hip.OUT_ROW_WORDS, _hip.ptr(lag), _hip.ptr(peak), _hip.ptr(r0), ld, _hip.ptr(ws),
+                                 ws.numel(), _hip.stream_handle(d))
         _hip.check(rc, "dsp_pitch_track")
         voiced = (peak > 0) & (self.vden * peak >= self.vnum * r0)
         rate = torch.tensor(float(self.sample_rate), dtype=torch.float64, device=d)
         f0 = torch.where(voiced, rate / lag.clamp(min=1).to(torch.float64), torch.zeros((), dtype=torch.float64, device=d))
         return dict(lag=lag, peak=peak, r0=r0, voiced=voiced, f0=f0)
-
-    def plain_frames(self):
-        """Frames of the last call that took the plain int64 path (one host sync)."""
-        import torch
-        return int(self._ws[:4].view(torch.int32).item())
 
 
 def f0_statistics(f0, voiced):
@@ -764,34 +791,23 @@ def lpc_window(window_type, L):
     return np.floor(create_window(window_type, int(L)) * 32768.0 + 0.5).astype(np.int32)
 
 
-class LpcAnalyzer:
+class LpcAnalyzer(_CropFramePlan):
     """Launch plan for ``dsp_lpc_autocorr`` + ``dsp_lpc_solve`` (csrc/lpc.hip): the exact
     integer autocorrelation r(0..order) of every Q15-windowed crop frame, then the Levinson-Durbin
     recursion and ``n_cep`` LPC cepstra in bit-defined fp64.  It runs after a ``FeatureExtractor`` call, on
     that call's device outputs, like ``PitchTracker``.  The arguments are validated here, without a device."""
+    _takes, _plan = "the LPC analysis takes", "the LPC plan"
 
     def __init__(self, frame_length, frame_shift, order=12, n_cep=12, window_type='hamming', device=None):
-        for name, v in (("frame_length", frame_length), ("frame_shift", frame_shift), ("order", order),
-                        ("n_cep", n_cep)):
-            if isinstance(v, bool) or int(v) != v:
-                raise ValueError("%s must be an integer" % name)
-        self.L, self.S, self.p, self.Q = int(frame_length), int(frame_shift), int(order), int(n_cep)
-        if not 2 <= self.L <= 4096:
-            raise ValueError("frame_length must be in 2 .. 4096")
-        if self.S < 1:
-            raise ValueError("frame_shift must be positive")
+        super().__init__(device, frame_length, frame_shift, order=order, n_cep=n_cep)
+        self.p, self.Q = int(order), int(n_cep)
         if not 1 <= self.p <= min(32, self.L - 1):
             raise ValueError("order must be in 1 .. min(32, frame_length - 1)")
         if not 0 <= self.Q <= 64:
             raise ValueError("n_cep must be in 0 .. 64")
         self.window_type = window_type
         self.table = lpc_window(window_type, self.L)  # raises ValueError for an unknown window
-        self.device = device
-        self._ws = self._table_dev = None
-
-    def frames(self, max_len):
-        """Width of the per-frame outputs for clips of up to max_len samples (the widest crop)."""
-        return 1 if max_len <= self.L else (int(max_len) - self.L + self.S - 1) // self.S + 1
+        self._table_dev = None
 
     def __call__(self, pcm, extracted, offsets=None, max_len=None):
         """pcm, offsets: what the ``FeatureExtractor`` call was given (int16); ``extracted``: the dict
@@ -800,29 +816,8 @@ class LpcAnalyzer:
         zeros behind a clip's frames and in the rows of failed clips (the solve runs on all B ld rows,
         and a zero row solves to zeros)."""
         import torch
-        if str(getattr(pcm, "dtype", "")) not in ("int16", "torch.int16"):
-            raise ValueError("the LPC analysis takes int16 samples (16-bit stereo channel sums in int32 are not supported)")
-        if self.device is None:
-            self.device = _hip.require_device()
-        d = self.device
-        pcm = _as_device(pcm, torch.int16, d)
-        if offsets is None:
-            if pcm.dim() != 2:
-                raise ValueError("1-D packed pcm needs offsets")
-            B, N = pcm.shape
-            off = torch.arange(B + 1, dtype=torch.int64, device=d) * N
-            true_max = N
-        else:
-            off = _as_device(offsets, torch.int64, d)
-            B = off.numel() - 1
-            true_max = None
-        if max_len is None:
-            max_len = true_max if true_max is not None else (int(torch.max(off[1:] - off[:-1]).item()) if B > 0 else 1)
-        max_len = max(int(max_len), 1)
-        rows = extracted["rows"]
-        if rows.shape != (B, _hip.OUT_ROW_WORDS) or rows.dtype != torch.int32 or not rows.is_contiguous():
-            raise ValueError("extracted['rows'] must be the [B, 19] int32 rows of the same batch")
-        ld, p, Q = self.frames(max_len), self.p, self.Q
+        pcm, off, B, max_len, rows, ld = self._batch(pcm, extracted, offsets, max_len)
+        d, p, Q = self.device, self.p, self.Q
         r = torch.zeros((B, ld, p + 1), dtype=torch.int64, device=d)
         a = torch.empty((B, ld, p), dtype=torch.float64, device=d)
         k = torch.empty((B, ld, p), dtype=torch.float64, device=d)
@@ -830,28 +825,17 @@ class LpcAnalyzer:
         reached = torch.empty((B, ld), dtype=torch.int32, device=d)
         cep = torch.empty((B, ld, Q), dtype=torch.float64, device=d)
         lib = _hip.lib()
-        nbytes = lib.dsp_lpc_workspace_bytes(B, max_len, self.L, self.S, p)
-        if nbytes == 0:
-            raise ValueError("outside the LPC plan")
-        if self._ws is None or self._ws.numel() < nbytes:
-            self._ws = torch.zeros(nbytes, dtype=torch.uint8, device=d)
+        ws = self._workspace(lib.dsp_lpc_workspace_bytes(B, max_len, self.L, self.S, p))
         if self.table is not None and self._table_dev is None:
             self._table_dev = torch.as_tensor(self.table).to(d)
-        rc = lib.dsp_lpc_autocorr(_hip.ptr(pcm.reshape(-1)), _hip.ptr(off), B, max_len, self.L, self.S, p,
-                                  _hip.ptr(self._table_dev), _hip.ptr(rows[:, 15:]), _hip.ptr(rows[:, 17:]),
-                                  _hip.ptr(rows[:, 18:]), _hip.OUT_ROW_WORDS, _hip.ptr(r), ld, _hip.ptr(self._ws),
-                                  self._ws.numel(), _hip.stream_handle(d))
+        rc = lib.dsp_lpc_autocorr(_hip.ptr(pcm), _hip.ptr(off), B, max_len, self.L, self.S, p, _hip.ptr(self._table_dev),
+                                  _hip.ptr(rows[:, 15:]), _hip.ptr(rows[:, 17:]), _hip.ptr(rows[:, 18:]),
+                                  _hip.OUT_ROW_WORDS, _hip.ptr(r), ld, _hip.ptr(ws), ws.numel(), _hip.stream_handle(d))
         _hip.check(rc, "dsp_lpc_autocorr")
         rc = lib.dsp_lpc_solve(_hip.ptr(r), B * ld, p, Q, _hip.ptr(a), _hip.ptr(k), _hip.ptr(err), _hip.ptr(reached),
                                _hip.ptr(cep) if Q else None, _hip.stream_handle(d))
         _hip.check(rc, "dsp_lpc_solve")
         return dict(r=r, a=a, k=k, err=err, reached=reached, cep=cep)
-
-    def plain_frames(self):
-        """Frames of the last call that took a plain fallback path (one host sync); always 0, the lag sums
-        have none."""
-        import torch
-        return int(self._ws[:4].view(torch.int32).item())
 
 
 def lpcc_statistics(cep, lengths):

@@ -3,47 +3,23 @@ surface on it.  Every integer and every double is compared with the restatement 
 by assert_array_equal (doubles as their bit patterns): both halves are defined exactly, so there is no
 tolerance and no frame is left out."""
 import functools
-import wave
 
 import numpy as np
 import pytest
 from numpy.testing import assert_array_equal
 
+import crop_frame_cases as C
 import lpc_reference as R
 import pitch_reference as P
+from crop_frame_cases import Guarded, _write_wav, pack
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 96  # elements before and after each output
 FILL = -7  # r before the launch
-
-
-class Guarded:
-    """An output of ``shape`` between two guard rows of GUARD elements holding ``fill``, as is the
-    output itself: what the kernel leaves untouched still holds it."""
-
-    def __init__(self, shape, dtype, fill):
-        import torch
-        self.n, self.fill, self.shape = int(np.prod(shape)), fill, tuple(shape)
-        self.buf = torch.full((self.n + 2 * GUARD,), fill, dtype=dtype, device="cuda")
-        self.view = self.buf[GUARD:GUARD + self.n]
-
-    def get(self):
-        g = np.concatenate([self.buf[:GUARD].cpu().numpy(), self.buf[GUARD + self.n:].cpu().numpy()])
-        assert (g == self.fill).all(), "a guard row was written"
-        return self.view.cpu().numpy().reshape(self.shape)
 
 
 def bits(a):
     return np.ascontiguousarray(a, np.float64).view(np.uint64)
-
-
-def pack(clips, lead=0):
-    """int16 clips back to back behind ``lead`` samples that belong to no clip -> (pcm, offsets)."""
-    lens = np.array([len(c) for c in clips], np.int64)
-    off = lead + np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
-    pcm = np.concatenate([np.full(lead, 12345, np.int16)] + [np.asarray(c, np.int16) for c in clips] + [np.full(8, -12345, np.int16)])
-    return pcm, off
 
 
 def autocorr_raw(pcm_t, off_t, B, max_len, L, S, p, table_t, se, nf, status, stride, ld):
@@ -63,25 +39,17 @@ def autocorr_raw(pcm_t, off_t, B, max_len, L, S, p, table_t, se, nf, status, str
     return out.get(), int(ws[:4].view(torch.int32).item())
 
 
-def autocorr_given(clips, crops, L, S, p, table=None, status=None, ld=None, lead=0, n_frames=None, untouched=(), want=None):
-    """Hand-made clips with their crops given directly (separate arrays, out_stride = 0); ``untouched``:
-    clips the call must leave alone although their status is good; ``want``: a reference from an earlier
-    call with the same clips, crops and table.  -> (r, counter, reference, (se, nf, status))"""
+def autocorr_given(clips, crops, L, S, p, table=None, want=None, **kw):
+    """Hand-made clips with their crops given directly (crop_frame_cases.given, whose keywords these are);
+    ``want``: a reference from an earlier call with the same clips, crops and table.
+    -> (r, counter, reference, (se, nf, status))"""
     import torch
-    B = len(clips)
-    pcm, off = pack(clips, lead)
-    se = np.asarray(crops, np.int32).reshape(B, 2)
-    nf = np.array([P.frame_count(e - s, L, S) for s, e in se], np.int32) if n_frames is None else np.asarray(n_frames, np.int32)
-    status = np.zeros(B, np.int32) if status is None else np.asarray(status, np.int32)
-    ld = int(nf.max()) if ld is None else ld
-    max_len = max(len(c) for c in clips)
-    dev = lambda a: None if a is None else torch.as_tensor(np.asarray(a)).to("cuda")
-    got, count = autocorr_raw(dev(pcm), dev(off), B, max_len, L, S, p, dev(table), dev(se), dev(nf), dev(status), 0, ld)
+    g = C.given(clips, crops, L, S, **kw)
+    table_t = None if table is None else torch.as_tensor(np.asarray(table)).to("cuda")
+    got, count = autocorr_raw(g.pcm, g.off, g.B, g.max_len, L, S, p, table_t, *g.fields, g.stride, g.ld)
     if want is None:
-        skip = status.copy()
-        skip[list(untouched)] = 1
-        want = R.autocorr_batch(clips, se, nf, skip, L, S, p, table, ld, FILL)
-    return got, count, want, (se, nf, status)
+        want = R.autocorr_batch(clips, g.se, g.nf, g.skip, L, S, p, table, g.ld, FILL)
+    return got, count, want, (g.se, g.nf, g.status)
 
 
 def solve_raw(r, p, Q):
@@ -224,7 +192,7 @@ def test_full_scale_and_constant_clips():
 def test_untouched_rows():
     """ld smaller than nf; a failing status between two good ones (its rows keep the fill value) and a
     status with only flag bits set (processed); crops that do not lie inside their clip, a clip longer
-    than max_len and n_frames = 0 write nothing."""
+    than max_len and n_frames below 1 write nothing; an empty crop with one frame is processed."""
     import torch
     rng = np.random.default_rng(12)
     clips = [rng.integers(-5000, 5000, 3000 + 7 * j).astype(np.int16) for j in range(6)]
@@ -247,6 +215,12 @@ def test_untouched_rows():
     want = R.autocorr_batch(clips[:3], se, nf, [0, 0, 1], 1102, 441, 12, ham, 5, FILL)
     assert_array_equal(got, want)
     assert (got[2] == FILL).all()
+    # every condition of the gate in one batch (crop_frame_cases.gate_batch), as separate arrays and as rows
+    for stride in (0, 19):
+        got, count, want, _ = autocorr_given(p=8, stride=stride, **C.gate_batch())
+        assert_array_equal(got, want)
+        assert (got[C.GATE_UNTOUCHED] == FILL).all() and (got[[0, 2], :, 0] > 0).all() and count == 0
+        assert not got[8, 0].any() and (got[8, 1:] == FILL).all()  # the empty crop's one all-zero frame
 
 
 def crafted_rows(p):
@@ -408,23 +382,6 @@ def test_lpc_analyzer():
         an(np.zeros((2, 4000), np.int32), {"rows": None})
 
 
-def _write_wav(path, data, channels=1):
-    with wave.open(str(path), "wb") as w:
-        w.setnchannels(channels)
-        w.setsampwidth(2)
-        w.setframerate(44100)
-        w.writeframes(np.ascontiguousarray(data).tobytes())
-
-
-def _wav_tree(tmp_path, per_class, seed):
-    from src.synth import make_clip
-    for c in range(3):
-        d = tmp_path / ("w%d" % c)
-        d.mkdir()
-        for j in range(per_class):
-            _write_wav(d / ("s%d.wav" % j), make_clip(seed + 10 * c + j, n_samples=20000 + 1013 * j, label=c, n_classes=3))
-
-
 def test_extract_both_with_lpc(tmp_path):
     """extract_both(lpc=6) on 3 x 4 WAV files, with and without pitch=True: the columns of the calls
     without it stay in front, bit for bit; the six cepstra are the last sequence columns (behind f0) and
@@ -433,7 +390,7 @@ def test_extract_both_with_lpc(tmp_path):
     from src.audio_processing import load_wav_pcm
     from src.dataset import PCMDataset
     from src.pipeline import FeatureExtractor
-    _wav_tree(tmp_path, 4, 4000)
+    C.wav_tree(tmp_path, 4, 4000)
     ds = PCMDataset(str(tmp_path))
     X15, y, seq2, lengths = ds.extract_both(1102, 441)
     X27, y2, seq8, lengths2 = ds.extract_both(1102, 441, lpc=6)
@@ -474,7 +431,7 @@ def test_compare_with_lpc(tmp_path):
     from sklearn.model_selection import train_test_split
     from src.feature_extraction import normalize_features
     from src.models import create_classifier
-    _wav_tree(tmp_path, 5, 5000)
+    C.wav_tree(tmp_path, 5, 5000)
     res = cfm.compare(str(tmp_path), hmm=True, lpc=6)
     assert list(res) == ["KNN", "SVM", "Decision Tree", "HMM"]
     X27, X_seq, y, lengths = cfm.load_both_methods(str(tmp_path), lpc=6)

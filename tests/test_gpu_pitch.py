@@ -2,42 +2,18 @@
 Every integer is compared with the numpy restatement of tests/pitch_reference.py by assert_array_equal:
 the track is defined exactly, so there is no tolerance and no frame is left out."""
 import functools
-import wave
 
 import numpy as np
 import pytest
 from numpy.testing import assert_array_equal
 
+import crop_frame_cases as C
 import pitch_reference as P
+from crop_frame_cases import Guarded, _write_wav, pack
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 96  # elements before and after each output
 FILL = (-9, -7, -7)  # lag, peak, r0 before the launch
-
-
-class Guarded:
-    """An output of ``shape`` between two guard rows of GUARD elements holding ``fill``, as is the
-    output itself: what the kernel leaves untouched still holds it."""
-
-    def __init__(self, shape, dtype, fill):
-        import torch
-        self.n, self.fill = int(np.prod(shape)), fill
-        self.buf = torch.full((self.n + 2 * GUARD,), fill, dtype=dtype, device="cuda")
-        self.view = self.buf[GUARD:GUARD + self.n].view(*shape)
-
-    def get(self):
-        g = np.concatenate([self.buf[:GUARD].cpu().numpy(), self.buf[GUARD + self.n:].cpu().numpy()])
-        assert (g == self.fill).all(), "a guard row was written"
-        return self.view.cpu().numpy()
-
-
-def pack(clips, lead=0):
-    """int16 clips back to back behind ``lead`` samples that belong to no clip -> (pcm, offsets)."""
-    lens = np.array([len(c) for c in clips], np.int64)
-    off = lead + np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
-    pcm = np.concatenate([np.full(lead, 12345, np.int16)] + [np.asarray(c, np.int16) for c in clips] + [np.full(8, -12345, np.int16)])
-    return pcm, off
 
 
 def track_raw(pcm_t, off_t, B, max_len, L, S, lo, hi, se, nf, status, stride, ld):
@@ -57,23 +33,12 @@ def track_raw(pcm_t, off_t, B, max_len, L, S, lo, hi, se, nf, status, stride, ld
     return tuple(o.get() for o in out) + (int(ws[:4].view(torch.int32).item()),)
 
 
-def track_given(clips, crops, L, S, lo, hi, status=None, ld=None, lead=0, n_frames=None, untouched=()):
-    """Hand-made clips with their crops given directly (separate arrays, out_stride = 0); ``untouched``:
-    clips the call must leave alone although their status is good."""
-    import torch
-    B = len(clips)
-    pcm, off = pack(clips, lead)
-    se = np.asarray(crops, np.int32).reshape(B, 2)
-    nf = np.array([P.frame_count(e - s, L, S) for s, e in se], np.int32) if n_frames is None else np.asarray(n_frames, np.int32)
-    status = np.zeros(B, np.int32) if status is None else np.asarray(status, np.int32)
-    ld = int(nf.max()) if ld is None else ld
-    max_len = max(len(c) for c in clips)
-    dev = lambda a: torch.as_tensor(a).to("cuda")
-    got = track_raw(dev(pcm), dev(off), B, max_len, L, S, lo, hi, dev(se), dev(nf), dev(status), 0, ld)
-    skip = status.copy()
-    skip[list(untouched)] = 1
-    want = P.track_batch(clips, se, nf, skip, L, S, lo, hi, ld, FILL)
-    return got, want, (se, nf, status)
+def track_given(clips, crops, L, S, lo, hi, **kw):
+    """Hand-made clips with their crops given directly (crop_frame_cases.given, whose keywords these are)."""
+    g = C.given(clips, crops, L, S, **kw)
+    got = track_raw(g.pcm, g.off, g.B, g.max_len, L, S, lo, hi, *g.fields, g.stride, g.ld)
+    want = P.track_batch(clips, g.se, g.nf, g.skip, L, S, lo, hi, g.ld, FILL)
+    return got, want, (g.se, g.nf, g.status)
 
 
 def wide_frames(clips, se, nf, status, L, S, ld):
@@ -198,7 +163,8 @@ def test_tie_rule_and_single_lags():
 
 def test_short_ld_failed_clips_and_bad_crops():
     """ld smaller than nf; a failing status between two good ones (its rows keep the fill value) and a
-    status with only flag bits set (processed); crops that do not lie inside their clip are skipped."""
+    status with only flag bits set (processed); crops that do not lie inside their clip, a clip longer
+    than max_len and n_frames below 1 write nothing; an empty crop with one frame is processed."""
     rng = np.random.default_rng(12)
     clips = [rng.integers(-5000, 5000, 3000 + 7 * j).astype(np.int16) for j in range(6)]
     crops = [(0, 3000), (5, 2900), (11, 3014), (0, 3021), (-1, 2000), (100, 3036)]
@@ -213,6 +179,14 @@ def test_short_ld_failed_clips_and_bad_crops():
     got, want, _ = track_given(clips[:3], crops[:3], 1102, 441, 110, 735, n_frames=[3, 0, 6], status=[0, 0, 0], ld=6)
     same(got, want)
     assert (got[0][1] == FILL[0]).all() and (got[0][0, 3:] == FILL[0]).all()
+    # every condition of the gate in one batch (crop_frame_cases.gate_batch), as separate arrays and as rows
+    for stride in (0, 19):
+        got, want, (se, nf, st) = track_given(lo=2, hi=63, stride=stride, **C.gate_batch())
+        same(got, want)
+        for g, fill in zip(got, FILL):
+            assert (g[C.GATE_UNTOUCHED] == fill).all() and (g[8, 1:] == fill).all()
+        assert (got[0][[0, 2]] >= 2).all() and (got[2][[0, 2]] > 0).all()
+        assert (got[0][8, 0], got[1][8, 0], got[2][8, 0]) == (2, 0, 0)  # the empty crop's one all-zero frame
 
 
 def test_longest_frames_full_scale():
@@ -256,14 +230,6 @@ def test_pitch_tracker():
         tracker(np.zeros((2, 4000), np.int32), {"rows": None})
 
 
-def _write_wav(path, data, channels=1):
-    with wave.open(str(path), "wb") as w:
-        w.setnchannels(channels)
-        w.setsampwidth(2)
-        w.setframerate(44100)
-        w.writeframes(np.ascontiguousarray(data).tobytes())
-
-
 def test_extract_both_with_pitch(tmp_path):
     """extract_both(pitch=True) on 3 x 4 WAV files: the 15 columns and the (E, ZCR) sequences are those
     of the default call, bit for bit, the default call is what the extractor's raw outputs give, and
@@ -272,12 +238,7 @@ def test_extract_both_with_pitch(tmp_path):
     from src.audio_processing import load_wav_pcm
     from src.dataset import PCMDataset
     from src.pipeline import FeatureExtractor
-    from src.synth import make_clip
-    for c in range(3):
-        d = tmp_path / ("w%d" % c)
-        d.mkdir()
-        for j in range(4):
-            _write_wav(d / ("s%d.wav" % j), make_clip(4000 + 10 * c + j, n_samples=20000 + 1013 * j, label=c, n_classes=3))
+    C.wav_tree(tmp_path, 4, 4000)
     ds = PCMDataset(str(tmp_path))
     X15, y, seq2, lengths = ds.extract_both(1102, 441)
     X20, y2, seq3, lengths2 = ds.extract_both(1102, 441, pitch=True)
@@ -359,12 +320,7 @@ def test_compare_with_pitch(tmp_path):
     from sklearn.model_selection import train_test_split
     from src.feature_extraction import normalize_features
     from src.models import create_classifier
-    from src.synth import make_clip
-    for c in range(3):
-        d = tmp_path / ("w%d" % c)
-        d.mkdir()
-        for j in range(5):
-            _write_wav(d / ("s%d.wav" % j), make_clip(5000 + 10 * c + j, n_samples=30000 + 1013 * j, label=c, n_classes=3))
+    C.wav_tree(tmp_path, 5, 5000, n_samples=30000)
     res = cfm.compare(str(tmp_path), dtw=True, pitch=True)
     assert list(res) == ["KNN", "SVM", "Decision Tree", "KNN-DTW"]
     X20, X_seq, y, lengths = cfm.load_both_methods(str(tmp_path), pitch=True)

@@ -118,6 +118,8 @@ def test_pitch_tracker_validates_without_a_device():
         kw.update(bad)
         with pytest.raises(ValueError):
             PitchTracker(**kw)
+    with pytest.raises(ValueError):
+        t(np.zeros((2, 4000), np.int32), {"rows": None})  # int32 samples, refused before any device is asked for
     f0 = np.array([[100.0, 0.0, 300.0], [0.0, 0.0, 0.0]])
     voiced = np.array([[True, False, True], [False, False, False]])
     assert np.array_equal(f0_statistics(f0, voiced), np.stack([P.f0_stats(a, b) for a, b in zip(f0, voiced)]))

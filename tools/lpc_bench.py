@@ -7,12 +7,10 @@ Hamming table) and dsp_lpc_solve (Q = 12) on its packed rows at L = 1102, S = 44
 Timed with device events, the median of --replays calls after two warm-up calls, on buffers made once,
 all in one run:
   the fused extraction, dsp_pitch_track (lags 110 .. 735: the yardstick dsp_lpc_autocorr must not exceed),
-    dsp_lpc_autocorr, the two A/B builds of it -- the lag sums on the i8 matrix cores, pitch.hip's scheme
-    with one lag tile (lib/libdsp_lpc_mfma.so), and the shipped kernel with fp64 accumulators
-    (lib/libdsp_lpc_fp64.so) -- each checked equal on the whole batch and against the restatement on a
-    full-scale edge batch, and dsp_lpc_solve on all B ld rows;
-  dsp_lpc_autocorr and the matrix-core build again on the first --loud clips amplified 8 x and clipped to
-    int16 (recordings driven into full scale: the frames a byte-digit form sends to its plain path);
+    dsp_lpc_autocorr, checked against the restatement on a full-scale edge batch, and dsp_lpc_solve on all
+    B ld rows;
+  dsp_lpc_autocorr again on the first --loud clips amplified 8 x and clipped to int16 (recordings driven
+    into full scale);
   the frames on a plain fallback path (the workspace's counter: 0 by definition);
   the restatement (tests/lpc_reference.py) on every --sample-th clip, integers and doubles checked equal;
   the 3-NN accuracy on 300 host-synthesised labelled clips (seed 7, 80 / 20 stratified, random_state 42,
@@ -21,7 +19,6 @@ all in one run:
   with --corpus n > 0, compare(hmm=True, dtw=True) with and without lpc=6 on n labelled clips
     (src.synth.make_batch, the corpus of DESIGN.md §4.9) written as WAV files to a temporary directory."""
 import argparse
-import ctypes
 import json
 import os
 import sys
@@ -179,26 +176,10 @@ def main():
     r = torch.zeros((B, ld, P_ORDER + 1), dtype=torch.int64, device=dev)
     assert lib.dsp_lpc_workspace_bytes(B, N, L, S, P_ORDER) <= 256
 
-    def autocorr(entry, dst):
-        _hip.check(entry(_hip.ptr(pcm), _hip.ptr(off), B, N, L, S, P_ORDER, _hip.ptr(table), se, nfp, stp, _hip.OUT_ROW_WORDS,
-                         _hip.ptr(dst), ld, _hip.ptr(ws), 256, stream), "dsp_lpc_autocorr")
-
-    _, ms["lpc_autocorr"] = D.timed(lambda: autocorr(lib.dsp_lpc_autocorr, r), args.replays)
+    _, ms["lpc_autocorr"] = D.timed(lambda: _hip.check(lib.dsp_lpc_autocorr(
+        _hip.ptr(pcm), _hip.ptr(off), B, N, L, S, P_ORDER, _hip.ptr(table), se, nfp, stp, _hip.OUT_ROW_WORDS, _hip.ptr(r), ld,
+        _hip.ptr(ws), 256, stream), "dsp_lpc_autocorr"), args.replays)
     plain = int(ws[:4].view(torch.int32).item())
-    ab_forms, ab_entries = {}, {}
-    for name, so in (("matrix_cores", "libdsp_lpc_mfma.so"), ("fp64_accumulators", "libdsp_lpc_fp64.so")):
-        ab_path = os.path.join(os.path.dirname(_hip.LIB_PATH), so)
-        if not os.path.exists(ab_path):
-            continue
-        ab = ctypes.CDLL(ab_path).dsp_lpc_autocorr
-        ab.restype, ab.argtypes = lib.dsp_lpc_autocorr.restype, lib.dsp_lpc_autocorr.argtypes
-        r2 = torch.zeros_like(r)
-        _, ms["lpc_autocorr_" + name] = D.timed(lambda: autocorr(ab, r2), args.replays)
-        ab_forms[name] = dict(batch_equal=bool(torch.equal(r, r2)), plain_path_frames=int(ws[:4].view(torch.int32).item()),
-                              edge_batch=edge_batch(ab, dev))
-        ab_entries[name] = ab
-        del r2
-    ab_forms["shipped"] = dict(edge_batch=edge_batch(lib.dsp_lpc_autocorr, dev))
 
     # clipped recordings: the same crops, the samples amplified into full scale
     loud = None
@@ -207,16 +188,11 @@ def main():
         keep = pcm[:nl].clone()
         pcm[:nl] = (keep.to(torch.int32) * 8).clamp(-32768, 32767).to(torch.int16)
         r2 = torch.zeros((nl, ld, P_ORDER + 1), dtype=torch.int64, device=dev)
-        loud = dict(clips=nl, ms_median={}, plain_path_frames={})
-        for name, entry in [("shipped", lib.dsp_lpc_autocorr)] + [(k_, v_) for k_, v_ in ab_entries.items() if k_ == "matrix_cores"]:
-            _, t_ms = D.timed(lambda: _hip.check(entry(_hip.ptr(pcm), _hip.ptr(off), nl, N, L, S, P_ORDER, _hip.ptr(table), se, nfp,
-                                                       stp, _hip.OUT_ROW_WORDS, _hip.ptr(r2), ld, _hip.ptr(ws), 256, stream),
-                                                 "dsp_lpc_autocorr"), args.replays)
-            loud["ms_median"][name] = float(np.median(t_ms))
-            loud["plain_path_frames"][name] = int(ws[:4].view(torch.int32).item())
-            loud.setdefault("r", r2.clone())
-            loud["equal"] = bool(torch.equal(loud["r"], r2))
-        del loud["r"], r2
+        _, t_ms = D.timed(lambda: _hip.check(lib.dsp_lpc_autocorr(
+            _hip.ptr(pcm), _hip.ptr(off), nl, N, L, S, P_ORDER, _hip.ptr(table), se, nfp, stp, _hip.OUT_ROW_WORDS,
+            _hip.ptr(r2), ld, _hip.ptr(ws), 256, stream), "dsp_lpc_autocorr"), args.replays)
+        loud = dict(clips=nl, ms_median=float(np.median(t_ms)), plain_path_frames=int(ws[:4].view(torch.int32).item()))
+        del r2
         loud["frames"] = int(rows[:nl, 17][(rows[:nl, 18] & 0xFF) == 0].sum().item())
         pcm[:nl] = keep
         del keep
@@ -239,7 +215,7 @@ def main():
                n_cep=Q, window="hamming", clips_ok=int(ok.sum()), frames=frames, solve_rows=n_rows,
                ms_median=med, ms_all={name: [float(x) for x in v] for name, v in ms.items()},
                autocorr_no_slower_than_pitch_track=bool(med["lpc_autocorr"] <= med["pitch_track"]),
-               ab_forms=ab_forms, clipped_batch=loud, plain_path_frames=plain,
+               edge_batch=edge_batch(lib.dsp_lpc_autocorr, dev), clipped_batch=loud, plain_path_frames=plain,
                defined_multiply_adds=frames * sum(L - tau for tau in range(P_ORDER + 1)),
                frames_stopped_early=int((reached.view(B, ld).cpu().numpy()[ok][np.arange(ld)[None, :] < h[ok, 17][:, None]]
                                          < P_ORDER).sum()))
