@@ -8,23 +8,26 @@ uniform weights, scipy.stats.mode: smallest label on ties).
 ``TraditionalClassifier('svm')`` trains with scikit-learn's SVC (libsvm) exactly as the reference
 does -- a device SMO would converge to another dual solution -- and predicts the
 fitted RBF model on the device (csrc/svm.hip, dsp_svc_predict): libsvm's kernel
-sums and one-vs-one vote in fp64, each row certified against a derived rounding bound and the few
-uncertifiable rows answered by libsvm itself, so the labels are SVC.predict's.  Other kernels
-(linear, poly, sigmoid), sparse input and models outside the kernel's plan predict through
-scikit-learn as before.
+sums and one-vs-one vote in fp64, each row certified against a derived rounding bound.
 
 ``TraditionalClassifier('naive_bayes')`` keeps a complete scikit-learn ``GaussianNB`` in ``.model``
 and predicts it on the device (csrc/gnb.hip, dsp_gnb_predict): the joint log
-likelihood in fp64, each row's argmax certified against a derived rounding bound, uncertified rows
-answered by GaussianNB.predict.  ``fit`` on a float64 device tensor runs dsp_gnb_fit -- numpy's own
-sequential sums, so theta_, var_, epsilon_ and class_prior_ are GaussianNB.fit's bits -- and with
-host rows it is scikit-learn's fit.
+likelihood in fp64, each row's argmax certified against a derived rounding bound.  ``fit`` on a
+float64 device tensor runs dsp_gnb_fit -- numpy's own sequential sums, so theta_, var_, epsilon_ and
+class_prior_ are GaussianNB.fit's bits -- and with host rows it is scikit-learn's fit.
 
 ``TraditionalClassifier('decision_tree')`` trains with scikit-learn (the best-split search draws
 its feature order from scikit-learn's RNG and breaks ties by visiting order) and
 walks the fitted tree on the device (csrc/tree.hip, dsp_tree_predict): comparisons only, so
-``predict`` and ``apply`` are scikit-learn's with no tolerance.  Models outside the kernels' plans
-(sparse input, more than 64 classes, multi-output trees) predict through scikit-learn as before.
+``predict`` and ``apply`` are scikit-learn's with no tolerance.
+
+These three share one path (``TraditionalClassifier._certified``): the fitted model is uploaded once
+(``pipeline.SvcIndex`` / ``GnbIndex`` / ``TreeIndex``) and again when the model is refitted, host rows
+or float64 device rows are queried, and the rows the device did not settle -- near ties the bound
+cannot decide, for the tree a NaN or a value that is not finite as float32 -- are answered by the
+model's own method on those rows alone, so the labels are scikit-learn's.  A model or rows outside
+the kernel's plan (``Index.in_plan``: another SVC kernel, sparse input, more than 64 classes, a
+multi-output tree) go to scikit-learn entirely; ``last_predict_stats`` says which path ran.
 
 ``SequenceClassifier`` / ``create_classifier('dtw_knn')`` (an extension: the reference has no
 sequence classifier) is k-NN under dynamic time warping on the per-frame sequences (csrc/dtw.hip,
@@ -43,7 +46,7 @@ learning-rate sweep in one launch.
 """
 import numpy as np
 
-from .pipeline import GnbIndex, KnnIndex, SvcIndex, TreeIndex, gaussian_nb_fit
+from .pipeline import GnbIndex, KnnIndex, SvcIndex, TreeIndex, _as_host, gaussian_nb_fit
 
 
 def _is_device_f64(X):
@@ -51,42 +54,45 @@ def _is_device_f64(X):
     return isinstance(X, torch.Tensor) and X.is_cuda and X.dtype == torch.float64
 
 
+# the scikit-learn-backed types: the uploaded form of the fitted model and, from a query's outputs, the
+# rows the device did not settle (near ties of the certificate; for the tree a NaN or a value that is
+# not finite as float32)
+_DEVICE = {'svm': (SvcIndex, lambda pred, dec, certified: certified == 0),
+           'naive_bayes': (GnbIndex, lambda pred, jll, certified: certified == 0),
+           'decision_tree': (TreeIndex, lambda pred, leaf: pred < 0)}
+
+
 class TraditionalClassifier:
     """models.py:18-72: fit / predict / evaluate with the reference's hyper-parameters."""
 
     def __init__(self, classifier_type='knn', **kwargs):
         self.classifier_type = classifier_type
+        self._index = None  # the device's copy of the fitted model (knn: of the training set)
         if classifier_type == 'knn':
             self.n_neighbors = int(kwargs.get('n_neighbors', 3))
             self.model = None
-        elif classifier_type == 'naive_bayes':
+            return
+        if classifier_type == 'naive_bayes':
             from sklearn.naive_bayes import GaussianNB
             self.model = GaussianNB()
-            self._index = None
-            self.last_predict_stats = {'device': False, 'uncertified': 0}
         elif classifier_type == 'decision_tree':
             from sklearn.tree import DecisionTreeClassifier
             self.model = DecisionTreeClassifier(max_depth=kwargs.get('max_depth', None), random_state=42)
-            self._index = None
-            # uncertified: rows the device left unanswered (a NaN, or not finite as float32)
-            self.last_predict_stats = {'device': False, 'uncertified': 0}
         elif classifier_type == 'svm':
             from sklearn.svm import SVC
             self.model = SVC(C=kwargs.get('C', 1.0), kernel=kwargs.get('kernel', 'rbf'), random_state=42)
-            self._svc_index = None
-            # which path the last predict / decision_function took (device: dsp_svc_predict ran;
-            # uncertified: rows of it answered by libsvm)
-            self.last_predict_stats = {'device': False, 'uncertified': 0}
         else:
             raise ValueError(f"不支持的分类器类型: {classifier_type}")
+        # which path the last predict / apply / decision_function took (device: the kernel ran;
+        # uncertified: rows of it that the device did not settle)
+        self.last_predict_stats = {'device': False, 'uncertified': 0}
 
     def fit(self, X_train, y_train):
         if self.classifier_type != 'knn':
+            self._index = None  # the fitted model is uploaded at the first predict
             if self.classifier_type == 'naive_bayes' and _is_device_f64(X_train):
                 return self._fit_nb_device(X_train, y_train)
             self.model.fit(X_train, y_train)
-            if self.classifier_type == 'svm':
-                self._svc_index = None  # the fitted model is uploaded at the first predict
             return self
         X = np.asarray(X_train, dtype=np.float64)
         y = np.asarray(y_train)
@@ -105,43 +111,10 @@ class TraditionalClassifier:
         idx, dist, _ = self._index.query(np.asarray(X_test, dtype=np.float64))
         return dist.cpu().numpy(), idx.cpu().numpy().astype(np.int64)
 
-    # -- SVC prediction on the device (models.py:56-58 with the model of :44-47) ---------------
-    def _svc_on_device(self, X):
-        """The fitted model is an RBF SVC inside dsp_svc_predict's plan and X is dense."""
-        from scipy.sparse import issparse
-        m = self.model
-        n_classes = len(getattr(m, 'classes_', ()))
-        return (m.kernel == 'rbf' and not m.probability and not m.break_ties and not getattr(m, '_sparse', False)
-                and not issparse(X) and 2 <= n_classes <= 64 and 1 <= m.support_vectors_.shape[1] <= 4096)
-
-    def _svc_query(self, X, with_dec):
-        """(pred, dec, certified) as numpy arrays from the device, and the stats record."""
-        # uploaded once per fitted model (a refit, also one made on self.model directly, replaces
-        # the support vector array)
-        if self._svc_index is None or self._svc_index.source is not self.model.support_vectors_:
-            self._svc_index = SvcIndex(self.model)
-        X = np.asarray(X, dtype=np.float64)
-        stats = {}
-        pred, dec, cert = self._svc_index.query(X, with_dec=with_dec, stats=stats)
-        self.last_predict_stats = {'device': True, 'uncertified': int(stats.get('uncertified', 0))}
-        return X, pred.cpu().numpy(), dec.cpu().numpy() if with_dec else None, cert.cpu().numpy()
-
-    def decision_function(self, X):
-        """SVC.decision_function with decision_function_shape='ovo' ([n, C(C-1)/2]; [n] and
-        scikit-learn's flipped sign for two classes).  SVM only."""
-        if self.classifier_type != 'svm':
-            raise AttributeError("decision_function is the SVM's")
-        if not self._svc_on_device(X):
-            self.last_predict_stats = {'device': False, 'uncertified': 0}
-            return self.model._decision_function(X)
-        _, _, dec, _ = self._svc_query(X, True)
-        return -dec.ravel() if dec.shape[1] == 1 else dec
-
-    # -- Naive Bayes and Decision Tree on the device (models.py:37-43, :52-58) -----------------
     def _fit_nb_device(self, X, y):
         """GaussianNB.fit of device rows with dsp_gnb_fit; .model ends up a complete GaussianNB."""
         m = self.model
-        y = y.cpu().numpy() if hasattr(y, 'cpu') else np.asarray(y)
+        y = _as_host(y)
         classes, codes = np.unique(y, return_inverse=True)
         if X.dim() != 2 or X.shape[1] < 2 or len(classes) > 64 or m.priors is not None or len(y) != X.shape[0]:
             m.fit(X.cpu().numpy(), y)  # outside dsp_gnb_fit's plan (one column: numpy sums pairwise)
@@ -154,73 +127,52 @@ class TraditionalClassifier:
         m.class_prior_ = m.class_count_ / m.class_count_.sum()
         return self
 
-    def _on_device(self, X):
-        """The fitted model is inside dsp_gnb_predict's / dsp_tree_predict's plan and X is dense."""
-        from scipy.sparse import issparse
+    # -- SVC, Naive Bayes and Decision Tree on the device (models.py:37-47, :52-58) -------------
+    def _certified(self, X, method, answer, redo=True, **outputs):
+        """``method`` (the model's predict, apply or _decision_function) of X, computed on the device:
+        ``answer`` of the query's outputs as numpy arrays, and ``method``'s own result for the rows the
+        device did not settle.  A model or rows outside the kernel's plan are ``method``'s entirely."""
+        Index, unsettled = _DEVICE[self.classifier_type]
         m = self.model
-        if issparse(X):
-            return False
-        if self.classifier_type == 'naive_bayes':
-            theta = getattr(m, 'theta_', None)
-            return theta is not None and 1 <= theta.shape[1] <= 4096 and 1 <= theta.shape[0] <= 64
-        return (getattr(m, 'tree_', None) is not None and m.n_outputs_ == 1 and 1 <= m.n_features_in_ <= 4096)
-
-    def _device_labels(self, X, want_leaf=False):
-        """predict (or apply) of a Naive Bayes / Decision Tree model: the device's answer, and the
-        model's own for the rows the device did not certify or answer."""
-        m = self.model
-        nb = self.classifier_type == 'naive_bayes'
-        source = m.theta_ if nb else m.tree_
+        if not Index.in_plan(m, X):
+            self.last_predict_stats = {'device': False, 'uncertified': 0}
+            return method(X)
         # uploaded once per fitted model (a refit, also one made on self.model directly, replaces
-        # theta_ / tree_)
-        if self._index is None or self._index.source is not source:
-            self._index = GnbIndex(m) if nb else TreeIndex(m)
-        if not hasattr(X, 'cpu'):
+        # support_vectors_ / theta_ / tree_)
+        if self._index is None or self._index.source is not Index.source_of(m):
+            self._index = Index(m)
+        if not hasattr(X, 'cpu'):  # device rows stay where they are
             X = np.asarray(X, dtype=np.float64)
-        stats = {}
-        if nb:
-            pred, _, cert = self._index.query(X, stats=stats)
-            pred, redo = pred.cpu().numpy(), np.flatnonzero(cert.cpu().numpy() == 0)
-            n = stats['uncertified']
-        else:
-            pred, leaf = self._index.query(X, with_leaf=want_leaf, stats=stats)
-            pred = pred.cpu().numpy()
-            redo, n = np.flatnonzero(pred < 0), stats['unanswered']
-        self.last_predict_stats = {'device': True, 'uncertified': int(n)}
-        out = leaf.cpu().numpy().astype(np.int64) if want_leaf else m.classes_[np.maximum(pred, 0)]
-        if len(redo):  # near ties the bound cannot decide; rows with a NaN or an infinity (it may raise)
-            rows = X[redo].cpu().numpy() if hasattr(X, 'cpu') else X[redo]
-            out[redo] = m.apply(rows) if want_leaf else m.predict(rows)
-        return out
+        out = [None if t is None else t.cpu().numpy() for t in self._index.query(X, **outputs)]
+        rows = np.flatnonzero(unsettled(*out))
+        self.last_predict_stats = {'device': True, 'uncertified': len(rows)}  # (before method may raise)
+        y = answer(*out)
+        if redo and len(rows):
+            y[rows] = method(_as_host(X[rows]))
+        return y
+
+    def decision_function(self, X):
+        """SVC.decision_function with decision_function_shape='ovo' ([n, C(C-1)/2]; [n] and
+        scikit-learn's flipped sign for two classes).  SVM only."""
+        if self.classifier_type != 'svm':
+            raise AttributeError("decision_function is the SVM's")
+        # dec is within its derived bound on every row, certified or not: nothing is redone
+        return self._certified(X, self.model._decision_function, redo=False, with_dec=True,
+                               answer=lambda pred, dec, certified: -dec.ravel() if dec.shape[1] == 1 else dec)
 
     def apply(self, X):
         """DecisionTreeClassifier.apply: the leaf's node index per row, int64.  Decision tree only."""
         if self.classifier_type != 'decision_tree':
             raise AttributeError("apply is the decision tree's")
-        if not self._on_device(X):
-            self.last_predict_stats = {'device': False, 'uncertified': 0}
-            return self.model.apply(X)
-        return self._device_labels(X, want_leaf=True)
+        return self._certified(X, self.model.apply, lambda pred, leaf: leaf.astype(np.int64))
 
     def predict(self, X_test):
-        if self.classifier_type in ('naive_bayes', 'decision_tree'):
-            if self._on_device(X_test):
-                return self._device_labels(X_test)
-            self.last_predict_stats = {'device': False, 'uncertified': 0}
-            return self.model.predict(X_test)
-        if self.classifier_type == 'svm' and self._svc_on_device(X_test):
-            X, pred, _, cert = self._svc_query(X_test, False)
-            y = self.model.classes_[pred]
-            redo = np.flatnonzero(cert == 0)
-            if len(redo):  # near ties the rounding bound cannot decide: libsvm's own answer
-                y[redo] = self.model.predict(X[redo])
-            return y
-        if self.classifier_type != 'knn':
-            if self.classifier_type == 'svm':
-                self.last_predict_stats = {'device': False, 'uncertified': 0}
-            return self.model.predict(X_test)
-        _, _, pred = self._index.query(np.asarray(X_test, dtype=np.float64))
-        return self.classes_[pred.cpu().numpy()]
+        if self.classifier_type == 'knn':
+            _, _, pred = self._index.query(np.asarray(X_test, dtype=np.float64))
+            return self.classes_[pred.cpu().numpy()]
+        outputs = {'with_leaf': False} if self.classifier_type == 'decision_tree' else {}
+        return self._certified(X_test, self.model.predict, lambda pred, *_: self.model.classes_[np.maximum(pred, 0)],
+                               **outputs)
 
     def evaluate(self, X_test, y_test):
         from sklearn.metrics import accuracy_score, classification_report, confusion_matrix
@@ -252,12 +204,12 @@ def _as_padded(X, lengths):
         for i, x in enumerate(seqs):
             out[i, :len(x)] = x
     else:
-        out = np.array(X.cpu().numpy() if hasattr(X, 'cpu') else X, dtype=np.float64)
+        out = np.array(_as_host(X), dtype=np.float64)  # a copy: the padding is rewritten below
         if out.ndim != 3:
             raise ValueError("X must be a list of [n_i, F] arrays or a padded [N, T, F] array")
         if lengths is None:
             raise ValueError("a padded [N, T, F] array needs lengths: trailing zero rows could be real frames")
-        n = np.asarray(lengths.cpu().numpy() if hasattr(lengths, 'cpu') else lengths).astype(np.int32).reshape(-1)
+        n = _as_host(lengths).astype(np.int32).reshape(-1)
         if len(n) != len(out) or (len(n) and (n.min() < 1 or n.max() > out.shape[1])):
             raise ValueError("lengths must be one per sequence, in [1, %d]" % out.shape[1])
     valid = np.arange(out.shape[1])[None, :] < n[:, None]
@@ -395,7 +347,7 @@ class TemplateClassifier(SequenceClassifier):
         for t in range(self.n_iter):
             tmpl, inert = updater.update(tmpl, len_t)
             inertia[t] = inert.cpu().numpy()
-        self.templates_ = tmpl.cpu().numpy() if hasattr(tmpl, 'cpu') else tmpl
+        self.templates_ = _as_host(tmpl)
         self.template_lengths_, self.inertia_ = len_t.astype(np.int32), inertia
         self._fit_X, self._fit_n, self._codes = self.templates_, self.template_lengths_, np.arange(C, dtype=np.int32)
         self._index = None  # uploaded at the first query

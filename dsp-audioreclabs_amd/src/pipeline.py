@@ -31,6 +31,11 @@ def _as_device(x, dtype, device):
     return torch.as_tensor(np.array(x, copy=True, order="C")).to(device=device, dtype=dtype).contiguous()
 
 
+def _as_host(x, dtype=None):
+    """x as a numpy array: a tensor is downloaded, a numpy array is returned as it is (no copy)."""
+    return np.asarray(x.cpu().numpy() if hasattr(x, "cpu") else x, dtype=dtype)
+
+
 class FeatureExtractor:
     """Reusable launch plan for ``dsp_extract_features`` (outputs preallocated per batch size).
 
@@ -347,15 +352,14 @@ def _dtw_groups(groups, assign, Na, Nb):
     if (groups is None) == (assign is None):
         raise ValueError("pass either groups=(group_start, members) or assign")
     if assign is not None:
-        assign = np.asarray(assign.cpu().numpy() if hasattr(assign, "cpu") else assign).astype(np.int64).reshape(-1)
+        assign = _as_host(assign).astype(np.int64).reshape(-1)
         if assign.size != Nb or (assign.size and (assign.min() < -1 or assign.max() >= Na)):
             raise ValueError("assign must hold one index in [-1, %d) per b sequence" % Na)
         members = np.flatnonzero(assign >= 0)
         members = members[np.argsort(assign[members], kind="stable")]
         start = np.concatenate([[0], np.cumsum(np.bincount(assign[members], minlength=Na))])
     else:
-        start, members = (np.asarray(g.cpu().numpy() if hasattr(g, "cpu") else g).astype(np.int64).reshape(-1)
-                          for g in groups)
+        start, members = (_as_host(g).astype(np.int64).reshape(-1) for g in groups)
         if start.size != Na + 1 or start[0] != 0 or (np.diff(start) < 0).any() or start[-1] != members.size:
             raise ValueError("group_start must be [Na + 1], non-decreasing from 0 to len(members)")
     return start.astype(np.int32), members.astype(np.int32)
@@ -394,7 +398,7 @@ def dtw_align(a, len_a, b, len_b, groups=None, assign=None, window=None, with_ra
 def dtw_path(x, y, window=None):
     """The warping path of one pair of [n, F] / [m, F] arrays: (distance, path int64 [L, 2]), the
     cells (i, j) ascending from (0, 0) to (n-1, m-1), expanded on the host from dsp_dtw_align's ranges."""
-    x, y = (np.asarray(v.cpu().numpy() if hasattr(v, "cpu") else v, dtype=np.float64) for v in (x, y))
+    x, y = (_as_host(v, np.float64) for v in (x, y))
     x, y = (v.reshape(-1, 1) if v.ndim == 1 else v for v in (x, y))
     if x.ndim != 2 or y.ndim != 2 or len(x) < 1 or len(y) < 1:
         raise ValueError("x and y must be non-empty [n, F] arrays")
@@ -451,7 +455,7 @@ def dtw_barycenter(seqs, lengths, init, n_iter=10, window=None, check_finite=Tru
     squared DTW distances to the template that iteration t started from.  Stops early when an update
     returns the template bitwise unchanged; the result then equals running all ``n_iter``."""
     import torch
-    init = np.asarray(init.cpu().numpy() if hasattr(init, "cpu") else init, dtype=np.float64)
+    init = _as_host(init, np.float64)
     init = init.reshape(-1, 1) if init.ndim == 1 else init
     N = len(lengths)
     up = DbaUpdater(seqs, lengths, [0, N], np.arange(N), window, check_finite)
@@ -481,9 +485,8 @@ class HmmModelSet:
     without ``prev``)."""
 
     def __init__(self, mean, var, cnt, n_valid, n_states, trans_floor=1e-3, prev=None):
-        mean, var = (np.asarray(v.cpu().numpy() if hasattr(v, "cpu") else v, dtype=np.float64) for v in (mean, var))
-        cnt, n_valid, n_states = (np.asarray(v.cpu().numpy() if hasattr(v, "cpu") else v).astype(np.int64)
-                                  for v in (cnt, n_valid, n_states))
+        mean, var = (_as_host(v, np.float64) for v in (mean, var))
+        cnt, n_valid, n_states = (_as_host(v).astype(np.int64) for v in (cnt, n_valid, n_states))
         if mean.ndim != 3 or var.shape != mean.shape or cnt.shape != mean.shape[:2]:
             raise ValueError("mean and var must be [C, Smax, F] and cnt [C, Smax]")
         C, Smax, _ = mean.shape
@@ -851,67 +854,131 @@ def lpcc_statistics(cep, lengths):
     return out
 
 
-class SvcIndex:
+class _ModelIndex:
+    """What ``SvcIndex``, ``GnbIndex`` and ``TreeIndex`` share: a fitted scikit-learn model uploaded once,
+    float64 rows [Nq, D] in, class indices out, the rows the device cannot settle marked for the caller
+    to answer with the model itself.  A subclass states its plan (the limits and ``_model_in_plan``),
+    the fitted attribute a model's upload is recognised by (``_source``), the C entry (``_call``) with
+    its leading arguments (``_args``, the model's), and a launch's rows and scratch.  One query at a
+    time per index (the workspace is a launch's scratch)."""
+
+    DMAX, CMIN, CMAX = 4096, 1, 64  # the kernels' plans: 1 <= D <= DMAX features, CMIN <= classes <= CMAX
+    _counter = "uncertified"  # the stats key of a query's count
+
+    @classmethod
+    def source_of(cls, model):
+        """The object a refit replaces (None before the first fit): an index is the fitted model's
+        while ``index.source is source_of(model)``."""
+        return getattr(model, cls._source, None)
+
+    @classmethod
+    def in_plan(cls, model, X=None):
+        """model is fitted and inside the kernel's plan, and X is dense: what the constructor and
+        ``query`` take.  Asks neither a device nor the library."""
+        from scipy.sparse import issparse
+        return not issparse(X) and cls.source_of(model) is not None and cls._model_in_plan(model)
+
+    @classmethod
+    def _shape_in_plan(cls, D, C):
+        return 1 <= D <= cls.DMAX and cls.CMIN <= C <= cls.CMAX
+
+    def __init__(self, model):
+        if not self.in_plan(model):
+            raise ValueError("%s outside the device plan (fitted%s, 1 <= D <= %d, %d <= classes <= %d)"
+                             % (type(model).__name__, self._kind, self.DMAX, self.CMIN, self.CMAX))
+        self.device = _hip.require_device()
+        self.source = self.source_of(model)
+        self._ws = None
+
+    def _rows_per_launch(self, Nq):
+        return Nq  # the scratch does not grow with the rows
+
+    def _counter_offset(self, n):
+        return 0  # where a launch of n rows leaves its int32 count in the workspace
+
+    def _query(self, X, outputs, stats):
+        """The outputs of a query, one per entry of ``outputs``: (dtype,) for [Nq], (dtype, w) for
+        [Nq, w], None for an output not asked for.  The rows go through the C call in launches of
+        ``_rows_per_launch``; a dict passed as ``stats`` receives the launches' summed count."""
+        import torch
+        d = self.device
+        q = _as_device(X, torch.float64, d)
+        if q.dim() != 2 or q.shape[1] != self.D:
+            raise ValueError("X has shape %s, the model was fitted on %d features" % (tuple(q.shape), self.D))
+        Nq = q.shape[0]
+        outs = [None if o is None else torch.empty(Nq, *o[1:], dtype=o[0], device=d) for o in outputs]
+        predict, stream = getattr(_hip.lib(), self._call), _hip.stream_handle(d)
+        step, count = max(self._rows_per_launch(Nq), 1), 0
+        for lo in range(0, Nq, step):
+            n = min(step, Nq - lo)
+            nbytes = self._workspace_bytes(n)
+            if nbytes == 0:
+                raise ValueError("outside the device plan")
+            if self._ws is None or self._ws.numel() < nbytes:
+                self._ws = torch.empty(nbytes, dtype=torch.uint8, device=d)
+            # rows [lo, lo + n) of the queries and of every output (all of them: the usual single launch)
+            part = [q] + outs if n == Nq else [None if t is None else t[lo:lo + n] for t in [q] + outs]
+            at = [None if t is None else t.data_ptr() for t in part]
+            # after the model's own arguments the three predict calls end alike
+            rc = predict(*self._args, at[0], n, *at[1:], self._ws.data_ptr(), self._ws.numel(), stream)
+            _hip.check(rc, self._call)
+            if stats is not None:
+                off = self._counter_offset(n)
+                count += int(self._ws[off:off + 4].view(torch.int32).item())
+        if stats is not None:
+            stats[self._counter] = count
+        return outs
+
+
+class SvcIndex(_ModelIndex):
     """A fitted ``sklearn.svm.SVC(kernel='rbf')`` uploaded once for ``dsp_svc_predict``
     (csrc/svm.hip): libsvm's own arrays -- support_vectors_, _n_support, _dual_coef_, _intercept_,
     _gamma (the underscore attributes: the public ones are sign-flipped for two classes).
     ``query`` is SVC.predict's vote as class indices plus, per row, whether the device could certify
-    it; the caller answers uncertified rows with the model itself.  One query at a
-    time per index (the workspace is a launch's scratch)."""
+    it; the caller answers uncertified rows with the model itself."""
 
+    CMIN = 2
     WORKSPACE_CAP = 256 << 20  # a query batch is cut into launches whose scratch stays below this
+    _source, _call = "support_vectors_", "dsp_svc_predict"
+    _kind = " on dense rows with the rbf kernel, without probability or break_ties"
+
+    @classmethod
+    def _model_in_plan(cls, m):
+        return (m.kernel == 'rbf' and not m.probability and not m.break_ties and not getattr(m, '_sparse', False)
+                and cls._shape_in_plan(m.support_vectors_.shape[1], len(m.classes_)))
 
     def __init__(self, model):
         import torch
-        self.device = _hip.require_device()
-        self.source = model.support_vectors_  # the array this index was uploaded from
+        super().__init__(model)
         sv = np.asarray(self.source, dtype=np.float64)
         self.nSV, self.D = sv.shape
         self.C = len(model.classes_)
         self.P = self.C * (self.C - 1) // 2
         self.gamma = float(model._gamma)
-        if _hip.lib().dsp_svc_workspace_bytes(self.nSV, 1, self.D, self.C) == 0:
-            raise ValueError("SVC outside the device plan (1 <= D <= 4096, 2 <= classes <= 64)")
         self.sv = _as_device(sv, torch.float64, self.device)
         self.n_support = _as_device(model._n_support, torch.int32, self.device)
         self.dual_coef = _as_device(np.asarray(model._dual_coef_, dtype=np.float64).reshape(self.C - 1, self.nSV),
                                     torch.float64, self.device)
         self.intercept = _as_device(np.asarray(model._intercept_, dtype=np.float64).reshape(self.P),
                                     torch.float64, self.device)
-        self._ws = None
+        self._args = (*map(_hip.ptr, (self.sv, self.n_support, self.dual_coef, self.intercept)), self.nSV, self.D,
+                      self.C, self.gamma)
+
+    def _rows_per_launch(self, Nq):
+        return max(1024, self.WORKSPACE_CAP // (8 * self.C * self.C))  # (C (C-1) + C) doubles per row and part
+
+    def _workspace_bytes(self, n):
+        return _hip.lib().dsp_svc_workspace_bytes(self.nSV, n, self.D, self.C)
+
+    def _counter_offset(self, n):
+        return _hip.lib().dsp_svc_workspace_uncertified_offset(self.nSV, n, self.D, self.C)
 
     def query(self, X, with_dec=False, stats=None):
         """(pred int32 [Nq] class index, dec float64 [Nq, C(C-1)/2] with libsvm's signs or None,
         certified int32 [Nq]); a dict passed as ``stats`` receives "uncertified" (one host sync)."""
         import torch
-        d, L = self.device, _hip.lib()
-        q = _as_device(X, torch.float64, d)
-        if q.dim() != 2 or q.shape[1] != self.D:
-            raise ValueError("X has shape %s, the model was fitted on %d features" % (tuple(q.shape), self.D))
-        Nq = q.shape[0]
-        pred = torch.empty(Nq, dtype=torch.int32, device=d)
-        cert = torch.empty(Nq, dtype=torch.int32, device=d)
-        dec = torch.empty((Nq, self.P), dtype=torch.float64, device=d) if with_dec else None
-        # rows per launch: the scratch of a launch is (C (C-1) + C) doubles per row and part
-        step = max(1024, self.WORKSPACE_CAP // (8 * self.C * self.C))
-        uncertified = 0
-        for lo in range(0, Nq, step):
-            n = min(step, Nq - lo)
-            ws_bytes = L.dsp_svc_workspace_bytes(self.nSV, n, self.D, self.C)
-            if self._ws is None or self._ws.numel() < ws_bytes:
-                self._ws = torch.empty(ws_bytes, dtype=torch.uint8, device=d)
-            rc = L.dsp_svc_predict(_hip.ptr(self.sv), _hip.ptr(self.n_support), _hip.ptr(self.dual_coef),
-                                   _hip.ptr(self.intercept), self.nSV, self.D, self.C, self.gamma,
-                                   _hip.ptr(q[lo:lo + n]), n, _hip.ptr(pred[lo:lo + n]),
-                                   _hip.ptr(dec[lo:lo + n]) if with_dec else None, _hip.ptr(cert[lo:lo + n]),
-                                   _hip.ptr(self._ws), self._ws.numel(), _hip.stream_handle(d))
-            _hip.check(rc, "dsp_svc_predict")
-            if stats is not None:
-                off = L.dsp_svc_workspace_uncertified_offset(self.nSV, n, self.D, self.C)
-                uncertified += int(self._ws[off:off + 4].view(torch.int32).item())
-        if stats is not None:
-            stats["uncertified"] = uncertified
-        return pred, dec, cert
+        dec = (torch.float64, self.P) if with_dec else None
+        return tuple(self._query(X, [(torch.int32,), dec, (torch.int32,)], stats))
 
 
 def gaussian_nb_fit(X, y_codes, n_classes, var_smoothing=1e-9):
@@ -937,24 +1004,26 @@ def gaussian_nb_fit(X, y_codes, n_classes, var_smoothing=1e-9):
     return theta, var, count, eps
 
 
-class GnbIndex:
+class GnbIndex(_ModelIndex):
     """A fitted ``sklearn.naive_bayes.GaussianNB`` uploaded once for ``dsp_gnb_predict``
     (csrc/gnb.hip): theta_, var_ and the two per-class constants of _joint_log_likelihood, computed
     here with numpy exactly as scikit-learn does.  ``query`` is GaussianNB.predict's argmax as class
     indices plus, per row, whether the device could certify it; the caller answers
-    uncertified rows with the model itself.  One query at a time per index."""
+    uncertified rows with the model itself."""
 
     WORKSPACE_CAP = 256 << 20  # a query batch is cut into launches whose scratch stays below this
+    _source, _call, _kind = "theta_", "dsp_gnb_predict", ""
+
+    @classmethod
+    def _model_in_plan(cls, m):
+        return cls._shape_in_plan(m.theta_.shape[1], m.theta_.shape[0])
 
     def __init__(self, model):
         import torch
-        self.device = _hip.require_device()
-        self.source = model.theta_  # the array this index was uploaded from
+        super().__init__(model)
         theta = np.asarray(model.theta_, dtype=np.float64)
         var = np.asarray(model.var_, dtype=np.float64)
         self.C, self.D = theta.shape
-        if _hip.lib().dsp_gnb_workspace_bytes(1, self.D, self.C) == 0:
-            raise ValueError("GaussianNB outside the device plan (1 <= D <= 4096, 1 <= classes <= 64)")
         with np.errstate(divide='ignore'):
             log_prior = np.log(np.asarray(model.class_prior_, dtype=np.float64))
         nconst = -0.5 * np.sum(np.log(2.0 * np.pi * var), axis=1)
@@ -962,86 +1031,59 @@ class GnbIndex:
         self.var = _as_device(var, torch.float64, self.device)
         self.log_prior = _as_device(log_prior, torch.float64, self.device)
         self.nconst = _as_device(nconst, torch.float64, self.device)
-        self._ws = None
+        self._args = (*map(_hip.ptr, (self.theta, self.var, self.log_prior, self.nconst)), self.D, self.C)
+
+    def _rows_per_launch(self, Nq):
+        return max(1024, self.WORKSPACE_CAP // (16 * self.C))  # a launch's scratch: 2 C doubles per row
+
+    def _workspace_bytes(self, n):
+        return _hip.lib().dsp_gnb_workspace_bytes(n, self.D, self.C)
 
     def query(self, X, with_jll=False, stats=None):
         """(pred int32 [Nq] class index, jll float64 [Nq, C] or None, certified int32 [Nq]); a dict
         passed as ``stats`` receives "uncertified" (one host sync)."""
         import torch
-        d, L = self.device, _hip.lib()
-        q = _as_device(X, torch.float64, d)
-        if q.dim() != 2 or q.shape[1] != self.D:
-            raise ValueError("X has shape %s, the model was fitted on %d features" % (tuple(q.shape), self.D))
-        Nq = q.shape[0]
-        pred = torch.empty(Nq, dtype=torch.int32, device=d)
-        cert = torch.empty(Nq, dtype=torch.int32, device=d)
-        jll = torch.empty((Nq, self.C), dtype=torch.float64, device=d) if with_jll else None
-        step = max(1024, self.WORKSPACE_CAP // (16 * self.C))  # a launch's scratch: 2 C doubles per row
-        uncertified = 0
-        for lo in range(0, Nq, step):
-            n = min(step, Nq - lo)
-            ws_bytes = L.dsp_gnb_workspace_bytes(n, self.D, self.C)
-            if self._ws is None or self._ws.numel() < ws_bytes:
-                self._ws = torch.empty(ws_bytes, dtype=torch.uint8, device=d)
-            rc = L.dsp_gnb_predict(_hip.ptr(self.theta), _hip.ptr(self.var), _hip.ptr(self.log_prior),
-                                   _hip.ptr(self.nconst), self.D, self.C, _hip.ptr(q[lo:lo + n]), n,
-                                   _hip.ptr(pred[lo:lo + n]), _hip.ptr(jll[lo:lo + n]) if with_jll else None,
-                                   _hip.ptr(cert[lo:lo + n]), _hip.ptr(self._ws), self._ws.numel(),
-                                   _hip.stream_handle(d))
-            _hip.check(rc, "dsp_gnb_predict")
-            if stats is not None:
-                uncertified += int(self._ws[:4].view(torch.int32).item())
-        if stats is not None:
-            stats["uncertified"] = uncertified
-        return pred, jll, cert
+        jll = (torch.float64, self.C) if with_jll else None
+        return tuple(self._query(X, [(torch.int32,), jll, (torch.int32,)], stats))
 
 
-class TreeIndex:
+class TreeIndex(_ModelIndex):
     """A fitted single-output ``sklearn.tree.DecisionTreeClassifier`` uploaded once for
     ``dsp_tree_predict`` (csrc/tree.hip): tree_'s children, features and thresholds and every
     node's majority class.  ``query`` is predict (as class indices) and apply; a row with a NaN
     (scikit-learn's missing value) or a value that is not finite as float32 (scikit-learn refuses
-    it) comes back as -1, for the caller to hand to the model itself.  One query at a
-    time per index."""
+    it) comes back as -1, for the caller to hand to the model itself."""
+
+    CMAX = (1 << 31) - 1  # a class index is an int32
+    _source, _call, _kind, _counter = "tree_", "dsp_tree_predict", " with a single output", "unanswered"
+
+    @classmethod
+    def _model_in_plan(cls, m):
+        return m.n_outputs_ == 1 and cls._shape_in_plan(m.n_features_in_, m.n_classes_)
 
     def __init__(self, model):
         import torch
-        self.device = _hip.require_device()
-        t = model.tree_
-        self.source = t  # the tree this index was uploaded from
-        if model.n_outputs_ != 1:
-            raise ValueError("only single-output trees are inside the device plan")
+        super().__init__(model)
+        t = self.source
         self.n_nodes, self.max_depth, self.D = int(t.node_count), int(t.max_depth), int(model.n_features_in_)
-        ws_bytes = _hip.lib().dsp_tree_workspace_bytes(self.n_nodes)
-        if ws_bytes == 0 or not 1 <= self.D <= 4096:
-            raise ValueError("tree outside the device plan (1 <= D <= 4096, 1 <= nodes < 2^31)")
         leaf_class = np.argmax(t.value[:, 0, :], axis=1)
         self.left = _as_device(t.children_left, torch.int32, self.device)
         self.right = _as_device(t.children_right, torch.int32, self.device)
         self.feature = _as_device(t.feature, torch.int32, self.device)
         self.threshold = _as_device(t.threshold, torch.float64, self.device)
         self.leaf_class = _as_device(leaf_class, torch.int32, self.device)
-        self._ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
+        self._args = (*map(_hip.ptr, (self.left, self.right, self.feature, self.threshold, self.leaf_class)),
+                      self.n_nodes, self.max_depth, self.D)
+        self._nbytes = _hip.lib().dsp_tree_workspace_bytes(self.n_nodes)
+
+    def _workspace_bytes(self, n):
+        return self._nbytes  # the packed node table, whatever the rows
 
     def query(self, X, with_leaf=True, stats=None):
         """(pred int32 [Nq] class index or -1, leaf int32 [Nq] node index or -1, or None); a dict
         passed as ``stats`` receives "unanswered" (one host sync)."""
         import torch
-        d = self.device
-        q = _as_device(X, torch.float64, d)
-        if q.dim() != 2 or q.shape[1] != self.D:
-            raise ValueError("X has shape %s, the model was fitted on %d features" % (tuple(q.shape), self.D))
-        Nq = q.shape[0]
-        pred = torch.empty(Nq, dtype=torch.int32, device=d)
-        leaf = torch.empty(Nq, dtype=torch.int32, device=d) if with_leaf else None
-        rc = _hip.lib().dsp_tree_predict(_hip.ptr(self.left), _hip.ptr(self.right), _hip.ptr(self.feature),
-                                         _hip.ptr(self.threshold), _hip.ptr(self.leaf_class), self.n_nodes,
-                                         self.max_depth, self.D, _hip.ptr(q), Nq, _hip.ptr(pred), _hip.ptr(leaf),
-                                         _hip.ptr(self._ws), self._ws.numel(), _hip.stream_handle(d))
-        _hip.check(rc, "dsp_tree_predict")
-        if stats is not None:
-            stats["unanswered"] = int(self._ws[:4].view(torch.int32).item())
-        return pred, leaf
+        return tuple(self._query(X, [(torch.int32,), (torch.int32,) if with_leaf else None], stats))
 
 
 def zscore_fit(X):

@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import nb_tree_reference as R
+import predict_path_cases as cases
 from conftest import GOLDEN
 
 pytestmark = pytest.mark.gpu
@@ -364,23 +365,61 @@ def test_classifier_predicts_like_sklearn(golden, name):
     assert clf.last_predict_stats == {'device': True, 'uncertified': 2}
 
 
-def test_refit_uploads_again_and_device_fit_completes_the_model():
-    from sklearn.naive_bayes import GaussianNB
-    from src.models import create_classifier
+def test_a_query_cut_into_two_launches(golden, monkeypatch):
+    """(dsp_gnb_predict's row count is its argument 7.)"""
+    from src.pipeline import GnbIndex
+    cases.check_two_launches(monkeypatch, GnbIndex, "dsp_gnb_predict", 7, sk_models("c3")[0], golden["c3/X"],
+                             golden["c3/tie_X"], with_jll=True)
+
+
+@pytest.mark.parametrize("name", MODELS)
+def test_classifier_takes_device_rows(golden, name):
+    """Ordinary rows plus the special ones (the two near ties; for the tree a NaN), as host rows and as a
+    float64 device tensor."""
+    from src.models import TraditionalClassifier
+    nb, tree, _ = sk_models(name)
+    clf = TraditionalClassifier('naive_bayes')
+    clf.model = nb
+    cases.check_device_rows(clf, np.concatenate([golden[name + "/X"], golden[name + "/tie_X"]]), 2)
+    clf = TraditionalClassifier('decision_tree')
+    clf.model = tree
+    X = golden[name + "/X"].copy()
+    X[3, 0] = np.nan
+    cases.check_device_rows(clf, X, 1)
+
+
+def _blobs():
     rng = np.random.default_rng(4)
     centres = rng.normal(0.0, 1.0, (4, 15))
     lab = rng.integers(0, 4, 1400)
     X = centres[lab] + rng.normal(0.0, 1.0, (1400, 15))
-    Xtr, ytr, Xte = X[:1000], lab[:1000] * 2 + 1, X[1000:]
-    for kind in ('naive_bayes', 'decision_tree'):
-        clf = create_classifier(kind).fit(Xtr, ytr)
-        assert np.array_equal(clf.predict(Xte), clf.model.predict(Xte)) and clf.last_predict_stats['device'] is True
-        first = clf._index
-        assert np.array_equal(clf.predict(Xte[:10]), clf.model.predict(Xte[:10])) and clf._index is first
-        clf.model.fit(Xtr[:, :7], ytr)  # a refit made on the model directly: the upload follows the model
-        assert np.array_equal(clf.predict(Xte[:, :7]), clf.model.predict(Xte[:, :7])) and clf._index is not first
-        clf.fit(Xtr, ytr)
-        assert np.array_equal(clf.predict(Xte), clf.model.predict(Xte))
+    return X[:1000], lab[:1000] * 2 + 1, X[1000:], lab[1000:] * 2 + 1
+
+
+@pytest.mark.parametrize("kind", ["svm", "naive_bayes", "decision_tree"])
+def test_upload_follows_the_fitted_model(kind):
+    """One contract for the three scikit-learn-backed types: the upload is kept between predicts, made
+    again after a refit on the model itself, dropped by ``fit``; the labels are the model's own."""
+    from src.models import create_classifier
+    Xtr, ytr, Xte, _ = _blobs()
+    clf = create_classifier(kind).fit(Xtr, ytr)
+    assert clf._index is None
+    assert np.array_equal(clf.predict(Xte), clf.model.predict(Xte)) and clf.last_predict_stats['device'] is True
+    first = clf._index
+    assert np.array_equal(clf.predict(Xte[:10]), clf.model.predict(Xte[:10])) and clf._index is first
+    clf.model.fit(Xtr[:, :7], ytr)  # a refit made on the model directly: the upload follows the model
+    assert np.array_equal(clf.predict(Xte[:, :7]), clf.model.predict(Xte[:, :7])) and clf._index is not first
+    assert clf.last_predict_stats['device'] is True
+    clf.fit(Xtr, ytr)
+    assert clf._index is None
+    assert np.array_equal(clf.predict(Xte), clf.model.predict(Xte)) and clf.last_predict_stats['device'] is True
+
+
+def test_refit_uploads_again_and_device_fit_completes_the_model():
+    """(The refit half is test_upload_follows_the_fitted_model.)"""
+    from sklearn.naive_bayes import GaussianNB
+    from src.models import create_classifier
+    Xtr, ytr, Xte, yte = _blobs()
     # fit on device rows: .model is a complete GaussianNB with scikit-learn's own bits
     clf = create_classifier('naive_bayes').fit(torch.as_tensor(Xtr, device=DEV), ytr)
     want = GaussianNB().fit(Xtr, ytr)
@@ -389,7 +428,7 @@ def test_refit_uploads_again_and_device_fit_completes_the_model():
     assert clf.model.epsilon_ == want.epsilon_ and clf.model.n_features_in_ == 15
     assert np.array_equal(clf.model.predict(Xte), want.predict(Xte))
     assert np.array_equal(clf.predict(torch.as_tensor(Xte, device=DEV)), want.predict(Xte))
-    res = clf.evaluate(Xte, lab[1000:] * 2 + 1)
+    res = clf.evaluate(Xte, yte)
     assert np.array_equal(res['predictions'], want.predict(Xte))
 
 

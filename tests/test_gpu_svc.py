@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import predict_path_cases as cases
 import svc_reference as R
 from conftest import GOLDEN
 
@@ -216,6 +217,22 @@ def test_svc_index_surface(golden):
     assert pred.shape == (0,) and dec is None and cert.shape == (0,) and stats == {"uncertified": 0}
     with pytest.raises(ValueError):
         idx.query(np.zeros((3, 14)))
+
+
+def test_a_query_cut_into_two_launches(golden, monkeypatch):
+    """(dsp_svc_predict's row count is its argument 9.)"""
+    from src.pipeline import SvcIndex
+    cases.check_two_launches(monkeypatch, SvcIndex, "dsp_svc_predict", 9, sk_model(golden, "c10"), golden["c10/X"],
+                             golden["c10/tie_X"], with_dec=True)
+
+
+@pytest.mark.parametrize("name", MODELS)
+def test_classifier_takes_device_rows(golden, name):
+    """Ordinary rows plus the two near ties, as host rows and as a float64 device tensor."""
+    from src.models import TraditionalClassifier
+    clf = TraditionalClassifier('svm', C=1.0, kernel='rbf')
+    clf.model = sk_model(golden, name)
+    cases.check_device_rows(clf, np.concatenate([golden[name + "/X"], golden[name + "/tie_X"]]), 2)
 
 
 def test_evaluate_equals_sklearn():

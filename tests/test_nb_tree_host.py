@@ -189,6 +189,36 @@ def test_fit_needs_no_device_and_predict_raises_without_one(monkeypatch, kind):
             clf.apply(X)
 
 
+def test_in_plan_decides_on_the_host(monkeypatch):
+    """GnbIndex.in_plan / TreeIndex.in_plan ask no device: the ordinary fitted models are inside the plan;
+    65 classes, a two-output tree, sparse rows and unfitted models are outside it, and predict then is
+    scikit-learn's with the "off" record."""
+    import torch
+    from scipy.sparse import csr_matrix
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
+    from src.models import TraditionalClassifier
+    from src.pipeline import GnbIndex, TreeIndex
+    X, y = _data(9)
+    off = {'device': False, 'uncertified': 0}
+    for kind, Index in (("naive_bayes", GnbIndex), ("decision_tree", TreeIndex)):
+        clf = TraditionalClassifier(kind)
+        assert not Index.in_plan(clf.model, X)  # not fitted
+        clf.fit(X, y)
+        assert Index.in_plan(clf.model, X) and not Index.in_plan(clf.model, csr_matrix(X))
+    rng = np.random.default_rng(3)
+    Xm, ym = rng.normal(0, 1, (130, 3)), np.arange(130) % 65
+    many = TraditionalClassifier("naive_bayes").fit(Xm, ym)
+    many.last_predict_stats = None
+    assert not GnbIndex.in_plan(many.model, Xm) and GnbIndex.in_plan(many.model.fit(Xm, ym % 64), Xm)
+    many.model.fit(Xm, ym)
+    assert np.array_equal(many.predict(Xm), many.model.predict(Xm)) and many.last_predict_stats == off
+    two = TraditionalClassifier("decision_tree")
+    two.model.fit(X, np.stack([y, y[::-1]], axis=1))  # two outputs
+    two.last_predict_stats = None
+    assert not TreeIndex.in_plan(two.model, X)
+    assert np.array_equal(two.predict(X), two.model.predict(X)) and two.last_predict_stats == off
+
+
 def test_models_outside_the_plan_predict_through_sklearn(monkeypatch):
     """No device is touched: sparse rows, more than 64 classes, a multi-output tree."""
     import torch

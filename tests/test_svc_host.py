@@ -111,6 +111,34 @@ def test_linear_kernel_still_predicts_through_sklearn():
     assert np.array_equal(clf.decision_function(X), clf.model.decision_function(X))
 
 
+def test_in_plan_decides_on_the_host(monkeypatch):
+    """SvcIndex.in_plan asks no device: the ordinary fitted model is inside the plan; sparse rows, a model
+    fitted on sparse rows, a linear kernel and an unfitted model are outside it, and predict then is
+    scikit-learn's with the "off" record."""
+    import torch
+    from scipy.sparse import csr_matrix
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
+    from src.models import TraditionalClassifier
+    from src.pipeline import SvcIndex
+    rng = np.random.default_rng(7)
+    X = np.concatenate([rng.normal(-1, 1, (40, 4)), rng.normal(1, 1, (40, 4))])
+    y = np.repeat([2, 9], 40)
+    off = {'device': False, 'uncertified': 0}
+    clf = TraditionalClassifier('svm')
+    assert not SvcIndex.in_plan(clf.model, X)  # not fitted
+    clf.fit(X, y)
+    assert SvcIndex.in_plan(clf.model, X) and not SvcIndex.in_plan(clf.model, csr_matrix(X))
+    sparse = TraditionalClassifier('svm').fit(csr_matrix(X), y)
+    assert not SvcIndex.in_plan(sparse.model, csr_matrix(X)) and not SvcIndex.in_plan(sparse.model, X)
+    for rows in (csr_matrix(X), X):
+        sparse.last_predict_stats = None
+        assert np.array_equal(sparse.predict(rows), sparse.model.predict(rows)) and sparse.last_predict_stats == off
+    linear = TraditionalClassifier('svm', kernel='linear').fit(X, y)
+    assert not SvcIndex.in_plan(linear.model, X)
+    linear.last_predict_stats = None
+    assert np.array_equal(linear.predict(X), linear.model.predict(X)) and linear.last_predict_stats == off
+
+
 def test_rbf_predict_needs_the_device(monkeypatch):
     """Like every accelerated entry point: no quiet fall-back to the host."""
     import torch

@@ -48,7 +48,7 @@ def timed(fn):
 
 def bench_queries(clf, Q, name):
     from src.pipeline import SvcIndex
-    clf._svc_index = None
+    clf._index = None
     cold, y_dev = timed(lambda: clf.predict(Q))
     unc = clf.last_predict_stats['uncertified']
     warm, y_dev2 = timed(lambda: clf.predict(Q))
