@@ -1,0 +1,78 @@
+// csr_pairs.h -- what dtw_align.hip (alignment paths, DBA) and hmm.hip (Viterbi paths, re-estimation)
+// both do with a CSR pair list (group_start [groups + 1], members [P]: group c against the sequences
+// members[p], p in [group_start[c], group_start[c+1])):
+//   csr_walk         the tiles of a launch's groups dealt to its persistent waves, a lane per pair
+//   csr_zero_counts, csr_grid   the host side of the chunked re-estimations
+#pragma once
+#include <algorithm>
+
+#include "dtw_internal.h"
+
+namespace dsp {
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// A lane's pair of one tile: p the pair (inr: inside its group; outputs are written for those only),
+// row the lane's sequence (0 where the pair has none), len its length (0: nothing of the lane is used;
+// a member outside [0, N) or a length outside 1 .. T), lmax the largest len of the tile (wave-uniform).
+struct CsrLane {
+    int64_t p;
+    bool inr;
+    int row, len, lmax;
+};
+
+// Wave wv of G takes the tiles wv, wv + G, ... of the groups cg = 0 .. nc-1, a tile being 64 consecutive
+// pairs of ONE group, counted by walking group_start (wave-uniform: scalar loads): group cg has its
+// list's pairs inside the window [p_lo, p_hi), pair p being sequence members[p].  group_start == NULL:
+// every group has the pairs [p_lo, p_hi) and pair p is sequence p.  len [N] are the sequences' lengths, T
+// their padded width.  tile(cg, lane) runs once per tile with every lane of the wave active.
+template <class Tile>
+__device__ __forceinline__ void csr_walk(int G, int wv, int nc, const int32_t *__restrict__ group_start, int p_lo,
+                                         int p_hi, const int32_t *__restrict__ members,
+                                         const int32_t *__restrict__ len, int64_t N, int T, Tile tile)
+{
+    const int lane = (int)threadIdx.x;
+    int base = 0;  // tiles of the groups before cg, modulo G
+    for (int cg = 0; cg < nc; cg++) {
+        const int g0 = group_start ? clampi(group_start[cg], p_lo, p_hi) : p_lo;
+        const int g1 = group_start ? clampi(group_start[cg + 1], p_lo, p_hi) : p_hi;
+        if (g1 <= g0) continue;
+        const int nt = (int)(((int64_t)g1 - g0 + 63) / 64);
+        int t0 = wv - base;
+        if (t0 < 0) t0 += G;
+        base = (int)(((int64_t)base + nt) % G);
+        for (int t = t0; t < nt; t += G) {
+            CsrLane ln;
+            ln.p = (int64_t)g0 + (int64_t)t * 64 + lane;
+            ln.inr = ln.p < g1;
+            const int ref = ln.inr ? (group_start ? members[ln.p] : (int)ln.p) : -1;
+            const bool rok = ref >= 0 && ref < N;
+            ln.row = rok ? ref : 0;
+            ln.len = rok ? len[ref] : 0;
+            if (ln.len < 1 || ln.len > T) ln.len = 0;
+            ln.lmax = wave_max_uniform(ln.len);
+            tile(cg, ln);
+        }
+    }
+}
+
+// a [na] = 0 and b [nb] = 0 before the first pair chunk of a re-estimation.  A kernel, not a memset: the
+// call stays a chain of kernel launches, which is what a captured single-stream graph of it replays in order.
+static __global__ __launch_bounds__(256) void csr_zero_counts(int32_t *__restrict__ a, int64_t na,
+                                                              int32_t *__restrict__ b, int64_t nb)
+{
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < na + nb; e += (int64_t)gridDim.x * 256) {
+        if (e < na)
+            a[e] = 0;
+        else
+            b[e - na] = 0;
+    }
+}
+
+// blocks of 256 threads striding over elems elements
+static inline dim3 csr_grid(int64_t elems)
+{
+    return dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((elems + 255) / 256, 65536)));
+}
+
+}  // namespace dsp

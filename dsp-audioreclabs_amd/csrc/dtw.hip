@@ -183,8 +183,7 @@ static int dtw_launch_dp(hipStream_t s, const double *a_rows, const int32_t *len
     if (G < 1) return DSP_OK;
     dtw_launch_pad(s, a_rows, nq, Tq, F, a);
     DTW_LAUNCH_F(F, dtw_dp, dim3((unsigned)G), dim3(64), 0, s, a, len_a, nq, Tq, b, len_b, Nr, Tr, window, dist, edge)
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? DSP_OK : DSP_ERR_HIP + (int)e;
+    return dtw_launch_status();
 }
 
 }  // namespace dsp
@@ -218,8 +217,8 @@ static int dtw_run(const double *ref, const int32_t *len_ref, const int32_t *ref
         if (k < 1) continue;
         hipLaunchKernelGGL(dsp::dtw_topk, dim3((unsigned)std::min<int64_t>(nq, 65536)), dim3(64), 0, s, rows, nq, Nr,
                            k, q0, self_offset, ref_labels, idx, dist, pred);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return DSP_ERR_HIP + (int)e;
+        const int rc = dsp::dtw_launch_status();
+        if (rc != DSP_OK) return rc;
     }
     return DSP_OK;
 }

@@ -33,18 +33,20 @@
 //              After the tile's strips each lane walks its own path back through those words (at
 //              most n + m - 1 steps; a word is re-read only when the strip or the row changes) and
 //              writes lo / hi.  The walk clamps at i = 0 and j = 0, so it ends and stays inside the
-//              pair's words whatever the codes hold.  Waves are persistent: wave w of G takes the
-//              tiles w, w + G, ... of the launch's groups, counted by walking group_start (scalar
-//              loads, at most 1024 groups per launch), so the words and the edges are per wave and
-//              bounded whatever P is.
+//              pair's words whatever the codes hold.  Waves are persistent: csr_pairs.h's csr_walk
+//              (shared with hmm.hip) gives wave w of G the tiles w, w + G, ... of the launch's groups
+//              (at most 1024 per launch), so the words and the edges are per wave and bounded
+//              whatever P is.
 //   dba_sums   a thread per (pair, frame, channel): S_k from the pair's ranges, all pairs in parallel.
 //   dba_accumulate / dba_finish   a thread per (template, frame, channel): acc = acc + S_k over the
-//              chunk's pairs in list order, then the division.
+//              chunk's pairs in list order, then the division; csr_pairs.h's csr_zero_counts zeroes
+//              the counts first.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <algorithm>
 
+#include "csr_pairs.h"
 #include "dsp_audiorec.h"
 #include "dtw_internal.h"
 
@@ -54,8 +56,6 @@ static constexpr size_t DTW_ALIGN_WAVE_CAP = 1024u << 20;  // bytes of code word
 static constexpr size_t DTW_ALIGN_RANGE_CAP = 128u << 20;  // bytes of lo, hi and S_k per DBA pair chunk
 static constexpr int DTW_ALIGN_GCHUNK = 1024;              // groups per launch at most
 static constexpr int DBA_BATCH = 16;                       // members whose loads a DBA thread keeps in flight
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // The groups c = 0 .. nc-1 of this launch (apad, len_a and group_start already point at the first
 // one) and of their pairs those in [p_lo, p_hi).  dist is indexed by p; d2 (D(end) before the sqrt),
@@ -70,40 +70,25 @@ __global__ __launch_bounds__(64) void dtw_align_dp(const double *__restrict__ ap
                                                    int32_t *__restrict__ hi, double *__restrict__ edge_ws,
                                                    unsigned long long *dir_ws)
 {
-    const int lane = (int)threadIdx.x;
-    const int G = (int)gridDim.x, wv = (int)blockIdx.x;
+    const int lane = (int)threadIdx.x, wv = (int)blockIdx.x;
     const int smax = (Ta + DTW_STRIP - 1) / DTW_STRIP;
     double *__restrict__ edge = edge_ws + (size_t)wv * (size_t)Tb * 64 + lane;
     unsigned long long *dir = dir_ws + (size_t)wv * (size_t)smax * (size_t)Tb * 64 + lane;  // [strip][row][lane]
-    int base = 0;  // tiles of the groups before c, modulo G
-    for (int cg = 0; cg < nc; cg++) {
-        const int g0 = clampi(group_start[cg], p_lo, p_hi), g1 = clampi(group_start[cg + 1], p_lo, p_hi);
-        if (g1 <= g0) continue;
-        const int nt = (int)(((int64_t)g1 - g0 + 63) / 64);
-        int t0 = wv - base;
-        if (t0 < 0) t0 += G;
-        base = (int)(((int64_t)base + nt) % G);
-        if (t0 >= nt) continue;
-        const int n = len_a[cg];
-        const bool nok = n >= 1 && n <= Ta;
-        const double *__restrict__ q = apad + ((int64_t)cg * (Ta + DTW_STRIP) + DTW_STRIP) * F;  // frame 0
-        const int S = nok ? (n + DTW_STRIP - 1) / DTW_STRIP : 0;
-        for (int t = t0; t < nt; t += G) {
-            const int64_t p = (int64_t)g0 + (int64_t)t * 64 + lane;
-            const bool inr = p < g1;
-            const int ref = inr ? members[p] : -1;
-            const bool rok = ref >= 0 && ref < Nb;
-            int m = rok ? len_b[ref] : 0;
-            if (m < 1 || m > Tb) m = 0;
+    csr_walk(
+        (int)gridDim.x, wv, nc, group_start, p_lo, p_hi, members, len_b, Nb, Tb, [&](int cg, const CsrLane &ln) {
+            const int n = len_a[cg], m = ln.len;
+            const bool nok = n >= 1 && n <= Ta;
+            const double *__restrict__ q = apad + ((int64_t)cg * (Ta + DTW_STRIP) + DTW_STRIP) * F;  // frame 0
+            const int S = nok ? (n + DTW_STRIP - 1) / DTW_STRIP : 0;
+            const int64_t p = ln.p;
             double res = INFINITY;
-            const int mmax = wave_max_uniform(m);
-            if (nok && mmax > 0)
-                res = dtw_sweep<F, true>(q, b + (int64_t)(rok ? ref : 0) * Tb * F, n, m, mmax, window, Tb, edge,
+            if (nok && ln.lmax > 0)
+                res = dtw_sweep<F, true>(q, b + (int64_t)ln.row * Tb * F, n, m, ln.lmax, window, Tb, edge,
                                          lo ? dir : nullptr);
-            if (!inr) continue;
+            if (!ln.inr) return;
             if (dist) dist[p] = res < INFINITY ? sqrt(res) : (double)INFINITY;
             if (d2) d2[p - p_lo] = res;
-            if (!lo) continue;
+            if (!lo) return;
             int32_t *__restrict__ plo = lo + (p - p_lo) * Ta, *__restrict__ phi = hi + (p - p_lo) * Ta;
             int filled = 0;
             if (nok && m > 0) {
@@ -140,8 +125,7 @@ __global__ __launch_bounds__(64) void dtw_align_dp(const double *__restrict__ ap
                 plo[i] = -1;
                 phi[i] = -1;
             }
-        }
-    }
+        });
 }
 
 #pragma clang fp contract(off)
@@ -220,13 +204,6 @@ __global__ __launch_bounds__(256) void dba_accumulate(int F, const int32_t *__re
     }
 }
 
-// cnt = 0 before a group chunk's first pair chunk.  A kernel, not a memset: the call stays a chain of
-// kernel launches, which is what a captured single-stream graph of it replays in order.
-__global__ __launch_bounds__(256) void dba_begin(int32_t *__restrict__ cnt, int64_t total)
-{
-    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) cnt[e] = 0;
-}
-
 // acc / cnt, zeros behind the template's length; the template itself where nothing was summed
 __global__ __launch_bounds__(256) void dba_finish(const double *__restrict__ tmpl, const int32_t *__restrict__ len_t,
                                                   int nc, int Tt, int F, const int32_t *__restrict__ cnt,
@@ -299,8 +276,7 @@ static int align_launch(hipStream_t s, const AlignPlan &pl, void *ws, bool pad, 
     const int G = std::min(pl.G, align_waves(nc, p_hi - p_lo, Ta, Tb));
     DTW_LAUNCH_F(F, dtw_align_dp, dim3((unsigned)G), dim3(64), 0, s, apad, len_a + c0, group_start + c0, (int)nc, Ta, b,
                  len_b, Nb, Tb, members, (int)p_lo, (int)p_hi, window, dist, d2, lo, hi, edge, dir)
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? DSP_OK : DSP_ERR_HIP + (int)e;
+    return dtw_launch_status();
 }
 
 }  // namespace dsp
@@ -349,24 +325,23 @@ extern "C" int dsp_dtw_dba_update(const double *tmpl, const int32_t *len_t, int6
     int32_t *cnt = (int32_t *)(w + 2 * pl.ranges + pl.sums + pl.d2);
     for (int64_t c0 = 0; c0 < C; c0 += pl.nc) {
         const int64_t nc = std::min(pl.nc, C - c0), elems = nc * Tt * F;
-        const dim3 grid((unsigned)std::min<int64_t>((elems + 255) / 256, 65536)), block(256);
+        const dim3 grid = dsp::csr_grid(elems), block(256);
         double *out = tmpl_out + c0 * Tt * F, *in = inertia ? inertia + c0 : nullptr;
-        hipLaunchKernelGGL(dsp::dba_begin, grid, block, 0, s, cnt, elems);
+        hipLaunchKernelGGL(dsp::csr_zero_counts, grid, block, 0, s, cnt, elems, nullptr, 0);
         for (int64_t p_lo = 0; p_lo < P; p_lo += pl.pc) {
             const int64_t p_hi = std::min(P, p_lo + pl.pc);
             const int rc = dsp::align_launch(s, pl, workspace, p_lo == 0, tmpl, len_t, c0, nc, Tt, seqs, len_s, N, Ts,
                                              F, window, group_start, members, p_lo, p_hi, nullptr, d2, lo, hi);
             if (rc != DSP_OK) return rc;
-            const int64_t selems = (p_hi - p_lo) * Tt * F;
-            hipLaunchKernelGGL(dsp::dba_sums, dim3((unsigned)std::min<int64_t>((selems + 255) / 256, 65536)), block, 0, s,
-                               seqs, N, Ts, F, Tt, group_start + c0, (int)nc, members, (int)p_lo, (int)p_hi, lo, hi, sums);
+            hipLaunchKernelGGL(dsp::dba_sums, dsp::csr_grid((p_hi - p_lo) * Tt * F), block, 0, s, seqs, N, Ts, F, Tt,
+                               group_start + c0, (int)nc, members, (int)p_lo, (int)p_hi, lo, hi, sums);
             hipLaunchKernelGGL(dsp::dba_accumulate, grid, block, 0, s, F, group_start + c0, (int)nc, Tt, len_t + c0,
                                (int)p_lo, (int)p_hi, lo, hi, sums, d2, out, cnt, in);
         }
         hipLaunchKernelGGL(dsp::dba_finish, grid, block, 0, s, tmpl + c0 * Tt * F, len_t + c0, (int)nc, Tt, F, cnt, out,
                            in);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return DSP_ERR_HIP + (int)e;
+        const int rc = dsp::dtw_launch_status();
+        if (rc != DSP_OK) return rc;
     }
     return DSP_OK;
 }

@@ -1,6 +1,7 @@
 // dtw_internal.h -- what dtw.hip (distances, k nearest neighbours) and dtw_align.hip (alignment
 // paths, DBA) share: the plan's constants and host arithmetic, the F dispatch, and the dynamic
-// programme itself -- the row body dtw_row and the sweep of one tile's strips, dtw_sweep.
+// programme itself -- the row body dtw_row and the sweep of one tile's strips, dtw_sweep.  hmm.hip
+// takes the plan, the dispatch and the small helpers from here too (csr_pairs.h: the pair list).
 //
 // The sweep.  A wave owns a tile: ONE sequence of the uniform side (length n) against 64 sequences of
 // the lanes' side, lane l owning the pair (uniform, its own sequence of length m).  The uniform
@@ -47,6 +48,12 @@ static inline size_t dtw_pad_bytes(int64_t rows, int T, int F)
 }
 // out [rows, T + DTW_STRIP, F]: DTW_STRIP frames of zeros before each sequence of in [rows, T, F] (dtw.hip)
 void dtw_launch_pad(hipStream_t s, const double *in, int64_t rows, int T, int F, double *out);
+// what an entry point returns after its launches
+static inline int dtw_launch_status()
+{
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? DSP_OK : DSP_ERR_HIP + (int)e;
+}
 
 // launches KERNEL<F> for the plan's F = 1 .. 8; the arguments after KERNEL are hipLaunchKernelGGL's
 #define DTW_CASE_F(FF, KERNEL, ...)                   \

@@ -49,14 +49,17 @@
 //              workspace; each lane then walks its own path back (at most n - 1 steps, the row only
 //              decreases, so the walk ends inside the pair's words whatever the bits hold).
 //   hmm_label  smallest score per sequence, ties to the smaller index, -1 when every score is +inf.
+//              The tiles come from csr_pairs.h's csr_walk, dtw_align_dp's walk over the CSR list
+//              (dsp_hmm_score's "every model against all N": the walk without a list).
 //   hmm_pairs / hmm_sums / hmm_accumulate / hmm_finish   the re-estimation, as dba_sums /
 //              dba_accumulate / dba_finish: per-pair sums in parallel, then the ordered adds with the
-//              loads of 16 members issued together; hmm_begin (a kernel, not a memset) zeroes the counts.
+//              loads of 16 members issued together; csr_pairs.h's csr_zero_counts zeroes the counts.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <algorithm>
 
+#include "csr_pairs.h"
 #include "dsp_audiorec.h"
 #include "dtw_internal.h"
 
@@ -68,8 +71,6 @@ static constexpr int HMM_GCHUNK = 1024;                  // models per launch at
 static constexpr size_t HMM_WAVE_CAP = 256u << 20;       // bytes of direction words per launch
 static constexpr size_t HMM_SUMS_CAP = 128u << 20;       // bytes of X_k, Q_k and frame counts per pair chunk
 static constexpr int HMM_BATCH = 16;                     // members whose loads an accumulate thread keeps in flight
-
-__device__ __forceinline__ int hmm_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // rec [C][32][2 F + 3], see above; a model with an invalid n_states gets zeros (never read)
 __global__ __launch_bounds__(256) void hmm_pack(const double *__restrict__ mu, const double *__restrict__ w,
@@ -195,50 +196,33 @@ __global__ __launch_bounds__(64) void hmm_dp(const double *__restrict__ rec, con
                                              int32_t *__restrict__ seg, uint32_t *dir_ws)
 {
     constexpr int R = 2 * F + 3;
-    const int lane = (int)threadIdx.x;
-    const int G = (int)gridDim.x, wv = (int)blockIdx.x;
+    const int lane = (int)threadIdx.x, wv = (int)blockIdx.x;
     uint32_t *dir = DIR && seg ? dir_ws + (size_t)wv * (size_t)T * 64 + lane : nullptr;
-    int base = 0;  // tiles of the models before c, modulo G
-    for (int cg = 0; cg < nc; cg++) {
-        const int g0 = group_start ? hmm_clampi(group_start[cg], 0, P) : 0;
-        const int g1 = group_start ? hmm_clampi(group_start[cg + 1], 0, P) : (int)N;
-        if (g1 <= g0) continue;
-        const int nt = (int)(((int64_t)g1 - g0 + 63) / 64);
-        int t0 = wv - base;
-        if (t0 < 0) t0 += G;
-        base = (int)(((int64_t)base + nt) % G);
-        if (t0 >= nt) continue;
-        const int S = n_states[cg];
-        const bool sok = S >= 1 && S <= Smax;
-        const double *__restrict__ rc = rec + (size_t)cg * HMM_SMAX * R;
-        for (int t = t0; t < nt; t += G) {
-            const int64_t p = (int64_t)g0 + (int64_t)t * 64 + lane;
-            const bool inr = p < g1;
-            const int ref = inr ? (group_start ? members[p] : (int)p) : -1;
-            const bool rok = ref >= 0 && ref < N;
-            int n = rok ? len[ref] : 0;
-            if (n < 1 || n > T) n = 0;
-            const int nmax = wave_max_uniform(n);
-            double res = INFINITY;
-            if (sok && nmax > 0)
-                res = hmm_sweep<F, DIR>(rc, HMM_SMAX - S, x + (int64_t)(rok ? ref : 0) * T * F, n, nmax, dir);
-            if (!inr) continue;
-            if (score) score[group_start ? p : p * C + c0 + cg] = res;
-            if (!DIR || !seg) continue;
-            int32_t *__restrict__ ps = seg + p * Smax;
-            int filled = 0;
-            if (res < INFINITY) {
-                // the lane's own walk back: state s is slot s + 32 - S, that bit of a row's word
-                int s = S - 1;
-                for (int r = n - 1; r >= 1 && s > 0; r--)
-                    if ((dir[(size_t)r * 64] >> (s + HMM_SMAX - S)) & 1) ps[s--] = r;
-                for (; s > 0; s--) ps[s] = s;  // not reached with the sweep's own words
-                ps[0] = 0;
-                filled = S;
-            }
-            for (int i = filled; i < Smax; i++) ps[i] = -1;
-        }
-    }
+    csr_walk((int)gridDim.x, wv, nc, group_start, 0, group_start ? P : (int)N, members, len, N, T,
+             [&](int cg, const CsrLane &ln) {
+                 const int S = n_states[cg], n = ln.len;
+                 const bool sok = S >= 1 && S <= Smax;
+                 const double *__restrict__ rc = rec + (size_t)cg * HMM_SMAX * R;
+                 const int64_t p = ln.p;
+                 double res = INFINITY;
+                 if (sok && ln.lmax > 0)
+                     res = hmm_sweep<F, DIR>(rc, HMM_SMAX - S, x + (int64_t)ln.row * T * F, n, ln.lmax, dir);
+                 if (!ln.inr) return;
+                 if (score) score[group_start ? p : p * C + c0 + cg] = res;
+                 if (!DIR || !seg) return;
+                 int32_t *__restrict__ ps = seg + p * Smax;
+                 int filled = 0;
+                 if (res < INFINITY) {
+                     // the lane's own walk back: state s is slot s + 32 - S, that bit of a row's word
+                     int s = S - 1;
+                     for (int r = n - 1; r >= 1 && s > 0; r--)
+                         if ((dir[(size_t)r * 64] >> (s + HMM_SMAX - S)) & 1) ps[s--] = r;
+                     for (; s > 0; s--) ps[s] = s;  // not reached with the sweep's own words
+                     ps[0] = 0;
+                     filled = S;
+                 }
+                 for (int i = filled; i < Smax; i++) ps[i] = -1;
+             });
 }
 
 __global__ __launch_bounds__(256) void hmm_label(const double *__restrict__ score, int64_t N, int64_t C,
@@ -333,7 +317,7 @@ __global__ __launch_bounds__(256) void hmm_accumulate(int F, int Smax, const int
         const int64_t c = e / ((int64_t)F * Smax);
         const int S = n_states[c];
         if (S < 1 || S > Smax || s >= S) continue;
-        const int g0 = hmm_clampi(group_start[c], p_lo, p_hi), g1 = hmm_clampi(group_start[c + 1], p_lo, p_hi);
+        const int g0 = clampi(group_start[c], p_lo, p_hi), g1 = clampi(group_start[c + 1], p_lo, p_hi);
         const bool lead = s == 0 && f == 0;
         int count = cnt[e], nv = lead ? n_valid[c] : 0;
         double ax = accx[e], aq = accq[e], tot = lead ? total_out[c] : 0.0;
@@ -368,19 +352,6 @@ __global__ __launch_bounds__(256) void hmm_accumulate(int F, int Smax, const int
             n_valid[c] = nv;
             total_out[c] = tot;
         }
-    }
-}
-
-// cnt = 0 and n_valid = 0 before the first pair chunk.  A kernel, not a memset: the call stays a chain
-// of kernel launches, which is what a captured single-stream graph of it replays in order.
-__global__ __launch_bounds__(256) void hmm_begin(int32_t *__restrict__ cnt, int64_t total, int32_t *__restrict__ n_valid,
-                                                 int64_t C)
-{
-    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total + C; e += (int64_t)gridDim.x * 256) {
-        if (e < total)
-            cnt[e] = 0;
-        else
-            n_valid[e - total] = 0;
     }
 }
 
@@ -450,8 +421,6 @@ static HmmPlan hmm_plan(int64_t C, int64_t N, int64_t P, int T, int F, int Smax)
     return pl;
 }
 
-static dim3 hmm_grid(int64_t elems) { return dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((elems + 255) / 256, 65536))); }
-
 // hmm_dp<F, DIR> as DTW_LAUNCH_F wants it: a template of F alone
 template <int F>
 static constexpr auto hmm_dp_score = hmm_dp<F, false>;
@@ -468,7 +437,7 @@ static int hmm_run(hipStream_t s, const HmmPlan &pl, void *ws, const double *mu,
     double *rec = (double *)ws;
     uint32_t *dir = (uint32_t *)((char *)ws + pl.rec);
     const int R = 2 * F + 3;
-    hipLaunchKernelGGL(hmm_pack, hmm_grid(C * HMM_SMAX * R), dim3(256), 0, s, mu, w, g, stay, adv, n_states, C, Smax, F, rec);
+    hipLaunchKernelGGL(hmm_pack, csr_grid(C * HMM_SMAX * R), dim3(256), 0, s, mu, w, g, stay, adv, n_states, C, Smax, F, rec);
     for (int64_t c0 = 0; c0 < C; c0 += HMM_GCHUNK) {
         const int64_t nc = std::min<int64_t>(HMM_GCHUNK, C - c0);
         const int64_t tiles = group_start ? P / 64 + nc : nc * ((N + 63) / 64);
@@ -483,8 +452,7 @@ static int hmm_run(hipStream_t s, const HmmPlan &pl, void *ws, const double *mu,
                          len, N, T, gs, members, (int)P, score, seg, dir)
         }
     }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? DSP_OK : DSP_ERR_HIP + (int)e;
+    return dsp::dtw_launch_status();
 }
 
 }  // namespace dsp
@@ -512,9 +480,8 @@ extern "C" int dsp_hmm_score(const double *mu, const double *w, const double *g,
                                            nullptr, nullptr, 0, sc, nullptr);
         if (rc != DSP_OK) return rc;
     }
-    if (label) hipLaunchKernelGGL(dsp::hmm_label, dsp::hmm_grid(N), dim3(256), 0, s, sc, N, C, label);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? DSP_OK : DSP_ERR_HIP + (int)e;
+    if (label) hipLaunchKernelGGL(dsp::hmm_label, dsp::csr_grid(N), dim3(256), 0, s, sc, N, C, label);
+    return dsp::dtw_launch_status();
 }
 
 extern "C" int dsp_hmm_align(const double *mu, const double *w, const double *g, const double *stay, const double *adv,
@@ -555,18 +522,17 @@ extern "C" int dsp_hmm_accumulate(const double *mu_prev, const double *var_prev,
     int32_t *cntf = (int32_t *)(wsp + pl.plen + 2 * pl.sums);
     const int64_t elems = C * Smax * F;
     const dim3 block(256);
-    hipLaunchKernelGGL(dsp::hmm_begin, dsp::hmm_grid(elems + C), block, 0, s, cntf, elems, n_valid, C);
+    hipLaunchKernelGGL(dsp::csr_zero_counts, dsp::csr_grid(elems + C), block, 0, s, cntf, elems, n_valid, C);
     for (int64_t p_lo = 0; p_lo < P; p_lo += pl.pc) {
         const int64_t p_hi = std::min(P, p_lo + pl.pc), np = p_hi - p_lo;
-        hipLaunchKernelGGL(dsp::hmm_pairs, dsp::hmm_grid(np), block, 0, s, n_states, C, Smax, len, N, T, group_start,
+        hipLaunchKernelGGL(dsp::hmm_pairs, dsp::csr_grid(np), block, 0, s, n_states, C, Smax, len, N, T, group_start,
                            members, (int)p_lo, (int)p_hi, seg, plen);
-        hipLaunchKernelGGL(dsp::hmm_sums, dsp::hmm_grid(np * Smax * F), block, 0, s, x, T, F, Smax, members, (int)p_lo,
+        hipLaunchKernelGGL(dsp::hmm_sums, dsp::csr_grid(np * Smax * F), block, 0, s, x, T, F, Smax, members, (int)p_lo,
                            (int)p_hi, seg, plen, sx, sq);
-        hipLaunchKernelGGL(dsp::hmm_accumulate, dsp::hmm_grid(elems), block, 0, s, F, Smax, n_states, C, group_start,
+        hipLaunchKernelGGL(dsp::hmm_accumulate, dsp::csr_grid(elems), block, 0, s, F, Smax, n_states, C, group_start,
                            (int)p_lo, (int)p_hi, plen, sx, sq, score, mean, var, cntf, n_valid, total);
     }
-    hipLaunchKernelGGL(dsp::hmm_finish, dsp::hmm_grid(elems), block, 0, s, mu_prev, var_prev, n_states, C, Smax, F, cntf,
+    hipLaunchKernelGGL(dsp::hmm_finish, dsp::csr_grid(elems), block, 0, s, mu_prev, var_prev, n_states, C, Smax, F, cntf,
                        n_valid, var_floor, mean, var, cnt, total);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? DSP_OK : DSP_ERR_HIP + (int)e;
+    return dsp::dtw_launch_status();
 }

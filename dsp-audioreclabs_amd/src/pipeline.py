@@ -280,6 +280,20 @@ def _dtw_window(window):
     return -1 if window is None or int(window) < 0 else int(window)
 
 
+_DTW_SHAPE = "unsupported DTW shape (1 <= F <= 8, 1 <= T <= 1024)"
+
+
+def _grown(ws, nbytes, unsupported, device):
+    """The grow-only workspace of a call: ``nbytes`` is what its ``*_workspace_bytes`` function returned
+    (0: the shape is outside the plan, ValueError(unsupported)); ``ws`` is kept when it is large enough."""
+    import torch
+    if nbytes == 0:
+        raise ValueError(unsupported)
+    if ws is None or ws.numel() < nbytes:
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return ws
+
+
 def dtw_pairwise(a, len_a, b, len_b, window=None, check_finite=True):
     """Dynamic time warping distances (include/dsp_audiorec.h: dsp_dtw_pairwise) between the padded
     sequences a [Nq, Tq, F] and b [Nr, Tr, F] with their lengths -> dist float64 [Nq, Nr] on the
@@ -294,12 +308,9 @@ def dtw_pairwise(a, len_a, b, len_b, window=None, check_finite=True):
     dist = torch.empty((Nq, Nr), dtype=torch.float64, device=d)
     if Nq == 0 or Nr == 0:
         return dist
-    nbytes = _hip.lib().dsp_dtw_workspace_bytes(Nr, Nq, Tr, Tq, F, 1)
-    if nbytes == 0:
-        raise ValueError("unsupported DTW shape (1 <= F <= 8, 1 <= T <= 1024)")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=d)
+    ws = _grown(None, _hip.lib().dsp_dtw_workspace_bytes(Nr, Nq, Tr, Tq, F, 1), _DTW_SHAPE, d)
     rc = _hip.lib().dsp_dtw_pairwise(_hip.ptr(a), _hip.ptr(len_a), Nq, Tq, _hip.ptr(b), _hip.ptr(len_b), Nr, Tr, F,
-                                     _dtw_window(window), _hip.ptr(dist), _hip.ptr(ws), nbytes, _hip.stream_handle(d))
+                                     _dtw_window(window), _hip.ptr(dist), _hip.ptr(ws), ws.numel(), _hip.stream_handle(d))
     _hip.check(rc, "dsp_dtw_pairwise")
     return dist
 
@@ -384,13 +395,10 @@ def dtw_align(a, len_a, b, len_b, groups=None, assign=None, window=None, with_ra
     lo = torch.empty((P, Ta), dtype=torch.int32, device=d) if with_ranges else None
     hi = torch.empty((P, Ta), dtype=torch.int32, device=d) if with_ranges else None
     if P > 0:
-        nbytes = _hip.lib().dsp_dtw_align_workspace_bytes(Na, P, Ta, Tb, F)
-        if nbytes == 0:
-            raise ValueError("unsupported DTW shape (1 <= F <= 8, 1 <= T <= 1024)")
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=d)
+        ws = _grown(None, _hip.lib().dsp_dtw_align_workspace_bytes(Na, P, Ta, Tb, F), _DTW_SHAPE, d)
         rc = _hip.lib().dsp_dtw_align(_hip.ptr(a), _hip.ptr(len_a), Na, Ta, _hip.ptr(b), _hip.ptr(len_b), Nb, Tb, F,
                                       _dtw_window(window), _hip.ptr(start), _hip.ptr(members), P, _hip.ptr(dist),
-                                      _hip.ptr(lo), _hip.ptr(hi), _hip.ptr(ws), nbytes, _hip.stream_handle(d))
+                                      _hip.ptr(lo), _hip.ptr(hi), _hip.ptr(ws), ws.numel(), _hip.stream_handle(d))
         _hip.check(rc, "dsp_dtw_align")
     return dist, lo, hi, start, members
 
@@ -410,22 +418,35 @@ def dtw_path(x, y, window=None):
     return float(dist[0].item()), np.stack([i, j], axis=1)
 
 
-class DbaUpdater:
+class _PairListPlan:
+    """What the two training updaters on a CSR pair list (csrc/csr_pairs.h) share: the padded sequences
+    ``seqs`` [N, T, F] with ``len_s`` and the list ``start`` [C + 1], ``members`` [P] uploaded once, and one
+    workspace that only grows, held across iterations."""
+
+    def __init__(self, seqs, lengths, group_start, members, check_finite=True):
+        import torch
+        self.device = d = _hip.require_device()
+        self.seqs, self.len_s = _dtw_operand(seqs, lengths, d, check_finite)
+        self.N, self.T, self.F = self.seqs.shape
+        self.C = len(group_start) - 1
+        start, members = _dtw_groups((group_start, members), None, self.C, self.N)
+        self.P = int(members.size)
+        self.start, self.members = _as_device(start, torch.int32, d), _as_device(members, torch.int32, d)
+        self._ws = None
+
+    def _grow(self, nbytes, unsupported):
+        self._ws = _grown(self._ws, nbytes, unsupported, self.device)
+        return self._ws
+
+
+class DbaUpdater(_PairListPlan):
     """The sequences of a DBA run uploaded once with their CSR class lists; ``update`` is one
     ``dsp_dtw_dba_update`` call for all templates: (new templates [C, Tt, F], inertia [C]) on the
     device."""
 
     def __init__(self, seqs, lengths, group_start, members, window=None, check_finite=True):
-        import torch
-        self.device = d = _hip.require_device()
-        self.seqs, self.len_s = _dtw_operand(seqs, lengths, d, check_finite)
-        self.N, self.Ts, self.F = self.seqs.shape
-        self.C = len(group_start) - 1
-        self.start, self.members = _dtw_groups((group_start, members), None, self.C, self.N)
-        self.P = int(self.members.size)
-        self.start, self.members = _as_device(self.start, torch.int32, d), _as_device(self.members, torch.int32, d)
-        self.window = _dtw_window(window)
-        self._ws = None
+        super().__init__(seqs, lengths, group_start, members, check_finite)
+        self.Ts, self.window = self.T, _dtw_window(window)
 
     def update(self, tmpl, len_t):
         import torch
@@ -434,17 +455,13 @@ class DbaUpdater:
         C, Tt, F = tmpl.shape
         if C != self.C or F != self.F:
             raise ValueError("templates [%d, ., %d] for %d classes of %d channels" % (C, F, self.C, self.F))
-        nbytes = _hip.lib().dsp_dtw_align_workspace_bytes(C, self.P, Tt, self.Ts, F)
-        if nbytes == 0:
-            raise ValueError("unsupported DTW shape (1 <= F <= 8, 1 <= T <= 1024)")
-        if self._ws is None or self._ws.numel() < nbytes:
-            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=d)
+        ws = self._grow(_hip.lib().dsp_dtw_align_workspace_bytes(C, self.P, Tt, self.Ts, F), _DTW_SHAPE)
         out = torch.empty_like(tmpl)
         inertia = torch.empty(C, dtype=torch.float64, device=d)
         rc = _hip.lib().dsp_dtw_dba_update(_hip.ptr(tmpl), _hip.ptr(len_t), C, Tt, _hip.ptr(self.seqs),
                                            _hip.ptr(self.len_s), self.N, self.Ts, F, self.window, _hip.ptr(self.start),
                                            _hip.ptr(self.members), self.P, _hip.ptr(out), _hip.ptr(inertia),
-                                           _hip.ptr(self._ws), self._ws.numel(), _hip.stream_handle(d))
+                                           _hip.ptr(ws), ws.numel(), _hip.stream_handle(d))
         _hip.check(rc, "dsp_dtw_dba_update")
         return out, inertia
 
@@ -529,14 +546,7 @@ class HmmModelSet:
         return self._dev
 
 
-def _hmm_ws(ws, C, N, P, T, F, Smax, device):
-    import torch
-    nbytes = _hip.lib().dsp_hmm_workspace_bytes(C, N, P, T, F, Smax)
-    if nbytes == 0:
-        raise ValueError("unsupported HMM shape (1 <= F <= 8, 1 <= T <= 1024, 1 <= Smax <= %d)" % HMM_MAX_STATES)
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
-    return ws
+_HMM_SHAPE = "unsupported HMM shape (1 <= F <= 8, 1 <= T <= 1024, 1 <= Smax <= %d)" % HMM_MAX_STATES
 
 
 def _hmm_model_args(models, F, device):
@@ -560,32 +570,20 @@ def hmm_score(models, seqs, lengths, with_labels=False, check_finite=True, _ws=N
     score = torch.empty((N, C), dtype=torch.float64, device=d)
     label = torch.empty(N, dtype=torch.int32, device=d) if with_labels else None
     if N > 0:
-        ws = _hmm_ws(_ws, C, N, 0, T, F, Smax, d)
+        ws = _grown(_ws, _hip.lib().dsp_hmm_workspace_bytes(C, N, 0, T, F, Smax), _HMM_SHAPE, d)
         rc = _hip.lib().dsp_hmm_score(*margs, _hip.ptr(x), _hip.ptr(n), N, T, F, _hip.ptr(score), _hip.ptr(label),
                                       _hip.ptr(ws), ws.numel(), _hip.stream_handle(d))
         _hip.check(rc, "dsp_hmm_score")
     return score, label
 
 
-class HmmUpdater:
+class HmmUpdater(_PairListPlan):
     """The sequences of a Viterbi training run uploaded once with their CSR class lists (one group per
     model); the workspace is held across iterations.  ``align`` is one ``dsp_hmm_align`` call for all
     models, ``accumulate`` one ``dsp_hmm_accumulate`` call."""
 
-    def __init__(self, seqs, lengths, group_start, members, check_finite=True):
-        import torch
-        self.device = d = _hip.require_device()
-        self.seqs, self.len_s = _dtw_operand(seqs, lengths, d, check_finite)
-        self.N, self.T, self.F = self.seqs.shape
-        self.C = len(group_start) - 1
-        start, members = _dtw_groups((group_start, members), None, self.C, self.N)
-        self.P = int(members.size)
-        self.start, self.members = _as_device(start, torch.int32, d), _as_device(members, torch.int32, d)
-        self._ws = None
-
     def _workspace(self, Smax):
-        self._ws = _hmm_ws(self._ws, self.C, self.N, self.P, self.T, self.F, Smax, self.device)
-        return self._ws
+        return self._grow(_hip.lib().dsp_hmm_workspace_bytes(self.C, self.N, self.P, self.T, self.F, Smax), _HMM_SHAPE)
 
     def align(self, models, with_seg=True):
         """(score float64 [P], seg int32 [P, Smax] or None) of every listed pair."""

@@ -10,35 +10,9 @@ import pytest
 
 import dtw_align_reference as A
 import dtw_reference as R
+from device_outputs import Guarded, _dev, bits, csr
 
 pytestmark = pytest.mark.gpu
-
-GUARD = 96  # elements before and after each output
-
-
-def bits(x):
-    return np.ascontiguousarray(np.asarray(x, np.float64)).view(np.uint64)
-
-
-def _dev(x, dtype):
-    import torch
-    return torch.as_tensor(np.ascontiguousarray(x)).to("cuda", dtype)
-
-
-class Guarded:
-    """An output of ``shape`` between two guard rows of GUARD elements holding ``fill``, as is the
-    output itself: what the kernel leaves untouched still holds it."""
-
-    def __init__(self, shape, dtype, fill):
-        import torch
-        self.n, self.fill = int(np.prod(shape)), fill
-        self.buf = torch.full((self.n + 2 * GUARD,), fill, dtype=dtype, device="cuda")
-        self.view = self.buf[GUARD:GUARD + self.n].view(*shape)
-
-    def get(self):
-        g = np.concatenate([self.buf[:GUARD].cpu().numpy(), self.buf[GUARD + self.n:].cpu().numpy()])
-        assert (g == self.fill).all(), "a guard row was written"
-        return self.view.cpu().numpy()
 
 
 def align_raw(a, la, b, lb, start, members, window, with_dist=True, with_ranges=True):
@@ -98,11 +72,6 @@ def dba_raw(tmpl, lt, seqs, ls, start, members, window, with_inertia=True):
         assert (inertia == -7.0).all()
         inertia = None
     return out, inertia
-
-
-def csr(groups):
-    start = np.concatenate([[0], np.cumsum([len(g) for g in groups])]).astype(np.int32)
-    return start, np.array([r for g in groups for r in g], np.int32)
 
 
 def check_align(got, want):

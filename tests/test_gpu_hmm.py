@@ -9,42 +9,17 @@ import numpy as np
 import pytest
 
 import hmm_reference as H
+from device_outputs import Guarded, _dev, bits, csr
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 96  # elements before and after each output
 STATES = [1, 2, 5, 31, 32, 3, 32, 1, 7, 2, 5]  # C = 11, mixed within one model set
-
-
-def bits(x):
-    return np.ascontiguousarray(np.asarray(x, np.float64)).view(np.uint64)
-
-
-def _dev(x, dtype):
-    import torch
-    return torch.as_tensor(np.ascontiguousarray(x)).to("cuda", dtype)
 
 
 def _nan_after(x):
     """A float64 input followed by NaN: a read past its end would poison a result."""
     import torch
     return _dev(np.concatenate([np.asarray(x, np.float64).reshape(-1), np.full(64, np.nan)]), torch.float64)
-
-
-class Guarded:
-    """An output of ``shape`` between two guard rows of GUARD elements holding ``fill``, as is the
-    output itself: what the kernel leaves untouched still holds it."""
-
-    def __init__(self, shape, dtype, fill):
-        import torch
-        self.n, self.fill = int(np.prod(shape)), fill
-        self.buf = torch.full((self.n + 2 * GUARD,), fill, dtype=dtype, device="cuda")
-        self.view = self.buf[GUARD:GUARD + self.n].view(*shape)
-
-    def get(self):
-        g = np.concatenate([self.buf[:GUARD].cpu().numpy(), self.buf[GUARD + self.n:].cpu().numpy()])
-        assert (g == self.fill).all(), "a guard row was written"
-        return self.view.cpu().numpy()
 
 
 def _model_args(model):
@@ -138,11 +113,6 @@ def accumulate_raw(mu_prev, var_prev, n_states, x, n, start, members, seg, score
     assert rc == 0
     torch.cuda.synchronize()
     return tuple(o.get() for o in out)
-
-
-def csr(groups):
-    start = np.concatenate([[0], np.cumsum([len(g) for g in groups])]).astype(np.int32)
-    return start, np.array([r for g in groups for r in g], np.int32)
 
 
 def same_bits(got, want):
@@ -389,6 +359,37 @@ def test_accumulate_after_align():
     want = H.accumulate(model.mu, model.var, STATES, x, n, start, members, seg, score, 1e-3)
     assert want[3][5] == 0 and want[3][4] > 50
     check_accumulate(accumulate_raw(model.mu, model.var, STATES, x, n, start, members, seg, score, 1e-3), want)
+
+
+def test_accumulate_pair_chunks():
+    """More pairs than one pair chunk holds: at Smax = 32, F = 8 the plan sums 128 MiB / (32 (4 + 16 * 8))
+    = 31 775 pairs per chunk, and 31 800 pairs over two models (S = 1, 2) put the chunk boundary inside
+    the second group, 11 775 = 16 * 735 + 15 pairs behind its start.  cnt, n_valid, total and both sums
+    are carried across it.  Six sequences of 1 .. 3 frames reused through members; members -1 and N and
+    the one-frame sequences under the two-state model are skipped, on both sides of the boundary."""
+    Smax, F, T, N = 32, 8, 3, 6
+    chunk = (128 << 20) // (Smax * (4 + 16 * F))
+    sizes = [20000, 11800]
+    P = sum(sizes)
+    assert chunk == 31775 and P > chunk and sizes[0] < chunk and (chunk - sizes[0]) % 16 == 15
+    rng = np.random.default_rng(160)
+    x, n = rng.normal(0, 1, (N, T, F)), np.array([3, 1, 2, 3, 2, 1], np.int32)
+    S = np.array([1, 2])
+    members = rng.integers(0, N, P).astype(np.int32)
+    members[rng.choice(P, 40, replace=False)] = np.tile([-1, N], 20)
+    members[[chunk - 2, chunk + 1]] = [N, -1]
+    members[[chunk - 1, chunk]] = [0, 3]  # valid members on either side of the boundary
+    start = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+    owner = np.repeat(np.arange(2), sizes)
+    ok = (members >= 0) & (members < N)
+    seg = H.uniform_seg(np.where(ok, n[np.where(ok, members, 0)], 0), S[owner], Smax)
+    score = rng.uniform(1, 100, P)
+    mu_prev, var_prev = rng.normal(0, 1, (2, Smax, F)), rng.uniform(1, 2, (2, Smax, F))
+    want = H.accumulate(mu_prev, var_prev, S, x, n, start, members, seg, score, 1e-3)
+    short = int((ok & (n[np.where(ok, members, 0)] < 2))[sizes[0]:].sum())
+    assert want[3][0] == int(ok[:sizes[0]].sum()) < sizes[0]
+    assert want[3][1] == int(ok[sizes[0]:].sum()) - short and short > 1000
+    check_accumulate(accumulate_raw(mu_prev, var_prev, S, x, n, start, members, seg, score, 1e-3), want)
 
 
 def word_sequences(seed, per_class=20):

@@ -204,3 +204,47 @@ def test_abi_argument_checks():
                                                            ws, nws, None)
     assert acc(None, p, 1 << 30) == _hip.DSP_ERR_ARGS and acc(p, p, 1 << 30) == _hip.DSP_ERR_ARGS  # mean == mu_prev
     assert acc(q, None, 0) == _hip.DSP_ERR_WORKSPACE and acc(q, None, 0, C=0) == _hip.DSP_OK
+
+
+ALIGN_WORKSPACE = {  # dsp_dtw_align_workspace_bytes(Na, P, Ta, Tb, F); a pair chunk at Ta = 1024, F = 8 is 1820 pairs
+    (19, 0, 70, 70, 3): 2789632,
+    (19, 37, 70, 70, 3): 2870272,
+    (1, 1, 1, 1, 1): 2816,
+    (3, 100, 1, 1024, 1): 4198656,
+    (3, 100, 1024, 1, 1): 1744640,
+    (10, 1819, 1024, 1024, 8): 792586496,
+    (10, 1820, 1024, 1024, 8): 792660224,
+    (10, 1821, 1024, 1024, 8): 792660224,
+    (10, 8000, 1024, 1024, 8): 1207896320,
+    (1024, 5000, 33, 40, 2): 73042944,
+    (1025, 5000, 33, 40, 2): 73042944,
+    (5000, 300000, 33, 40, 2): 388566528,
+    (10 ** 9, (1 << 31) - 1, 1024, 1024, 8): 1309653248,
+}
+HMM_WORKSPACE = {  # dsp_hmm_workspace_bytes(C, N, P, T, F, Smax); a pair chunk at Smax = 32, F = 8 is 31 775 pairs
+    (0, 0, 0, 1, 1, 1): 1024,
+    (10, 100, 0, 64, 2, 5): 191232,
+    (10, 100, 100, 64, 2, 5): 225280,
+    (1, 1, 1, 1, 1, 1): 2816,
+    (3, 10, 100, 1024, 8, 32): 1488896,
+    (2, 6, 31774, 3, 8, 32): 134607872,
+    (2, 6, 31775, 3, 8, 32): 134612224,
+    (2, 6, 31776, 3, 8, 32): 134612224,
+    (2, 6, 31800, 3, 8, 32): 134612224,
+    (1024, 50, 5000, 8, 2, 4): 5254400,
+    (1025, 50, 5000, 8, 2, 4): 5256960,
+    (5000, 321, 300000, 8, 2, 4): 73548800,
+    (1 << 20, 1000, (1 << 31) - 2, 1024, 8, 32): 14965276672,
+}
+
+
+def test_workspace_sizes_are_recorded():
+    """The two pair-list workspaces byte for byte (the layouts behind them are part of what a caller
+    allocates once and keeps): P = 0, either side of a pair chunk, 1024 and 1025 groups, T = 1 and 1024,
+    and the largest shapes of the plans.  The values are those of the library before csrc/csr_pairs.h."""
+    from src import _hip
+    lib = _hip.load_library()
+    for args, want in ALIGN_WORKSPACE.items():
+        assert lib.dsp_dtw_align_workspace_bytes(*args) == want, args
+    for args, want in HMM_WORKSPACE.items():
+        assert lib.dsp_hmm_workspace_bytes(*args) == want, args
