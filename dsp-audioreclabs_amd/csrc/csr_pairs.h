@@ -1,8 +1,9 @@
-// csr_pairs.h -- what dtw_align.hip (alignment paths, DBA) and hmm.hip (Viterbi paths, re-estimation)
-// both do with a CSR pair list (group_start [groups + 1], members [P]: group c against the sequences
+// csr_pairs.h -- what dtw_align.hip (alignment paths, DBA), hmm.hip (Viterbi paths, re-estimation) and
+// vq.hip (nearest codewords, Lloyd re-estimation) do with a CSR pair list (group_start [groups + 1], members [P]: group c against the sequences
 // members[p], p in [group_start[c], group_start[c+1])):
 //   csr_walk         the tiles of a launch's groups dealt to its persistent waves, a lane per pair
 //   csr_zero_counts, csr_grid   the host side of the chunked re-estimations
+//   csr_label        the label of a score matrix [N, C] (hmm.hip, vq.hip)
 #pragma once
 #include <algorithm>
 
@@ -66,6 +67,25 @@ static __global__ __launch_bounds__(256) void csr_zero_counts(int32_t *__restric
             a[e] = 0;
         else
             b[e - na] = 0;
+    }
+}
+
+// label [N]: the column of the smallest score [N, C] (never NaN) per row, ties to the smaller index, -1
+// when every score is +inf
+static __global__ __launch_bounds__(256) void csr_label(const double *__restrict__ score, int64_t N, int64_t C,
+                                                        int32_t *__restrict__ label)
+{
+    for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < N; r += (int64_t)gridDim.x * 256) {
+        double best = INFINITY;
+        int32_t arg = -1;
+        for (int64_t c = 0; c < C; c++) {
+            const double v = score[r * C + c];
+            if (v < best) {
+                best = v;
+                arg = (int32_t)c;
+            }
+        }
+        label[r] = arg;
     }
 }
 

@@ -48,9 +48,10 @@
 //              a row is one 32-bit word per lane, stored [row][lane] in the wave's area of the
 //              workspace; each lane then walks its own path back (at most n - 1 steps, the row only
 //              decreases, so the walk ends inside the pair's words whatever the bits hold).
-//   hmm_label  smallest score per sequence, ties to the smaller index, -1 when every score is +inf.
 //              The tiles come from csr_pairs.h's csr_walk, dtw_align_dp's walk over the CSR list
 //              (dsp_hmm_score's "every model against all N": the walk without a list).
+//   csr_label  (csr_pairs.h) smallest score per sequence, ties to the smaller index, -1 when every
+//              score is +inf.
 //   hmm_pairs / hmm_sums / hmm_accumulate / hmm_finish   the re-estimation, as dba_sums /
 //              dba_accumulate / dba_finish: per-pair sums in parallel, then the ordered adds with the
 //              loads of 16 members issued together; csr_pairs.h's csr_zero_counts zeroes the counts.
@@ -223,23 +224,6 @@ __global__ __launch_bounds__(64) void hmm_dp(const double *__restrict__ rec, con
                  }
                  for (int i = filled; i < Smax; i++) ps[i] = -1;
              });
-}
-
-__global__ __launch_bounds__(256) void hmm_label(const double *__restrict__ score, int64_t N, int64_t C,
-                                                 int32_t *__restrict__ label)
-{
-    for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < N; r += (int64_t)gridDim.x * 256) {
-        double best = INFINITY;
-        int32_t arg = -1;
-        for (int64_t c = 0; c < C; c++) {
-            const double v = score[r * C + c];
-            if (v < best) {
-                best = v;
-                arg = (int32_t)c;
-            }
-        }
-        label[r] = arg;
-    }
 }
 
 // ---- re-estimation ----
@@ -480,7 +464,7 @@ extern "C" int dsp_hmm_score(const double *mu, const double *w, const double *g,
                                            nullptr, nullptr, 0, sc, nullptr);
         if (rc != DSP_OK) return rc;
     }
-    if (label) hipLaunchKernelGGL(dsp::hmm_label, dsp::csr_grid(N), dim3(256), 0, s, sc, N, C, label);
+    if (label) hipLaunchKernelGGL(dsp::csr_label, dsp::csr_grid(N), dim3(256), 0, s, sc, N, C, label);
     return dsp::dtw_launch_status();
 }
 

@@ -37,6 +37,9 @@ of the training set (csrc/dtw_align.hip, dsp_dtw_dba_update).
 ``HmmClassifier`` / ``create_classifier('hmm')`` keeps one left-to-right Gaussian HMM per class, trained
 by Viterbi re-estimation (csrc/hmm.hip, dsp_hmm_score / dsp_hmm_align / dsp_hmm_accumulate, DESIGN.md
 §4.10): scores, state paths and re-estimated models defined bit for bit.
+``VqClassifier`` / ``create_classifier('vq')`` keeps one vector-quantisation codebook per class, trained by
+LBG binary splitting (csrc/vq.hip, dsp_vq_score / dsp_vq_assign / dsp_vq_accumulate):
+nearest codewords, distortions and re-estimated codebooks defined bit for bit.
 
 ``MLPTrainer`` (models.py:109-221) trains the reference's MLP with the fused on-device trainer
 (csrc/mlp.hip: dsp_mlp_train / dsp_mlp_predict) -- the whole serial SGD loop of
@@ -448,6 +451,95 @@ class HmmClassifier(SequenceClassifier):
         return self.classes_[label]
 
 
+class VqClassifier(SequenceClassifier):
+    """One vector-quantisation codebook per class, trained by LBG binary splitting, and the label of the
+    codebook with the smallest total quantisation distortion -- the cheapest of the three classical
+    isolated-word recognisers at prediction time: no time alignment, one nearest-codeword search per
+    frame and class.  csrc/vq.hip (dsp_vq_score, dsp_vq_assign, dsp_vq_accumulate).
+    Input handling and normalisation are ``SequenceClassifier``'s.
+
+    n_codes    codewords per codebook: a power of two in 1 .. 256.
+    n_iter     Lloyd rounds per level at most (>= 1).
+    eps        the split and repair offset (normalised units), added to / subtracted from every channel.
+    ``fit`` runs all classes in every device call.  The one-codeword start is each class's centroid (an
+    ``accumulate`` with all-zero codes and a zero previous codebook).  Then, until ``n_codes`` is reached:
+    ``pipeline.vq_split``, and rounds of assign -> accumulate -> ``pipeline.vq_repair_empty``; a level ends
+    when a round gives every member the codes of the round before it (never after the level's first
+    round) or after ``n_iter`` rounds.  A class with fewer valid frames than ``n_codes`` raises ValueError.
+    After ``fit``: codebooks_ float64 [C, K, F] (normalised units), counts_ int64 [C, K] (each cell's frames
+    in the last accumulate, before the repair), totals_ float64 [rounds run, C] (row t: each class's total
+    distortion under the codebook round t started from), n_iter_ the rounds run.
+    ``score_samples`` is the average distortion per frame, D / n (the divide in numpy).
+    No CPU path: ``fit`` and ``predict`` raise HipError without a HIP device (constructing needs none).
+    """
+
+    def __init__(self, n_codes=16, n_iter=10, eps=0.01, normalize=True):
+        super().__init__(n_neighbors=1, window=None, normalize=normalize)
+        from .pipeline import VQ_MAX_CODES
+        if isinstance(n_codes, bool) or not isinstance(n_codes, (int, np.integer)):
+            raise ValueError("n_codes must be an int")
+        if not 1 <= n_codes <= VQ_MAX_CODES or n_codes & (n_codes - 1):
+            raise ValueError("n_codes must be a power of two in [1, %d]" % VQ_MAX_CODES)
+        self.n_codes, self.n_iter, self.eps = int(n_codes), int(n_iter), float(eps)
+        if self.n_iter < 1 or not self.eps > 0.0 or not np.isfinite(self.eps):
+            raise ValueError("n_iter must be >= 1 and eps a positive number")
+
+    def fit(self, X, y, lengths=None):
+        from .pipeline import VqUpdater, vq_repair_empty, vq_split
+        X, n, codes = self._training_set(X, y, lengths)
+        C, F = len(self.classes_), X.shape[2]
+        order = np.argsort(codes, kind="stable")  # each class's members in training order
+        start = np.concatenate([[0], np.cumsum(np.bincount(codes, minlength=C))])
+        frames = np.bincount(codes, weights=n, minlength=C)
+        if (frames < self.n_codes).any():
+            c = int(np.argmax(frames < self.n_codes))
+            raise ValueError("class %r has %d frames, fewer than n_codes = %d" % (self.classes_[c], frames[c], self.n_codes))
+        updater = VqUpdater(X, n, start, order, check_finite=False)
+        K, sizes = 1, np.ones(C, np.int32)
+        stats = updater.accumulate(np.zeros((C, 1, F)), sizes, np.zeros((len(order), X.shape[1]), np.int32),
+                                   np.zeros(len(order)))
+        cb, cnt = _as_host(stats[0]), _as_host(stats[1]).astype(np.int64)
+        totals = []
+        while K < self.n_codes:
+            cb, K = vq_split(cb, self.eps), 2 * K
+            sizes = np.full(C, K, np.int32)
+            code = None
+            for _ in range(self.n_iter):
+                dist, new_code = updater.assign(cb, sizes)
+                stats = updater.accumulate(cb, sizes, new_code, dist)
+                totals.append(_as_host(stats[3]))
+                cnt = _as_host(stats[1]).astype(np.int64)
+                cb, _ = vq_repair_empty(stats[0], cnt, sizes, self.eps)
+                new_code = _as_host(new_code)
+                same = code is not None and np.array_equal(new_code, code)
+                code = new_code
+                if same:
+                    break
+        self.codebooks_, self.counts_, self.n_iter_ = cb, cnt, len(totals)
+        self.totals_ = np.array(totals, dtype=np.float64).reshape(len(totals), C)
+        return self
+
+    def _scores(self, X, lengths, with_labels):
+        from .pipeline import vq_score
+        Xq, nq = _as_padded(X, lengths)
+        if Xq.shape[2] != self.codebooks_.shape[2]:
+            raise ValueError("X has %d feature channels, the fitted codebooks %d" % (Xq.shape[2], self.codebooks_.shape[2]))
+        sizes = np.full(len(self.codebooks_), self.codebooks_.shape[1], np.int32)
+        return vq_score(self.codebooks_, sizes, self._scale(Xq, nq), nq, with_labels=with_labels, check_finite=False), nq
+
+    def score_samples(self, X, lengths=None):
+        """float64 [n, C]: each sequence's average distortion per frame under each class's codebook."""
+        (score, _), nq = self._scores(X, lengths, False)
+        return score.cpu().numpy() / nq.astype(np.float64)[:, None]
+
+    def kneighbors(self, X, lengths=None):
+        raise NotImplementedError("a VQ classifier keeps no training sequences")
+
+    def predict(self, X, lengths=None):
+        (_, label), _ = self._scores(X, lengths, True)
+        return self.classes_[label.cpu().numpy()]
+
+
 # ==================== MLP (models.py:77-221) ====================
 
 def _build_network(input_size, hidden_layers, num_classes, dropout):
@@ -714,8 +806,8 @@ def fit_mlp_models(X_train, y_train, input_size, hidden_layers, num_classes, lea
 
 
 def create_classifier(classifier_type, **kwargs):
-    """models.py:226-246.  'mlp' takes MLPTrainer's arguments; 'dtw_knn', 'dtw_template' and 'hmm' (extensions) are the
-    SequenceClassifier, the TemplateClassifier and the HmmClassifier.  A bare ``create_classifier('mlp')``
+    """models.py:226-246.  'mlp' takes MLPTrainer's arguments; 'dtw_knn', 'dtw_template', 'hmm' and 'vq' (extensions) are
+    the SequenceClassifier, the TemplateClassifier, the HmmClassifier and the VqClassifier.  A bare ``create_classifier('mlp')``
     raises NotImplementedError naming them (the reference fails there with a TypeError)."""
     if classifier_type in ['knn', 'naive_bayes', 'decision_tree', 'svm']:
         return TraditionalClassifier(classifier_type, **kwargs)
@@ -725,6 +817,8 @@ def create_classifier(classifier_type, **kwargs):
         return TemplateClassifier(**kwargs)
     if classifier_type == 'hmm':
         return HmmClassifier(**kwargs)
+    if classifier_type == 'vq':
+        return VqClassifier(**kwargs)
     if classifier_type == 'mlp':
         if not kwargs:
             raise NotImplementedError("create_classifier('mlp') needs input_size, hidden_layers and num_classes "

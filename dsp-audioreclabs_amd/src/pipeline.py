@@ -656,6 +656,146 @@ def hmm_uniform_segmentation(lengths, n_states, Smax):
     return np.where((s < S[:, None]) & (n >= S)[:, None], seg, -1).astype(np.int32)
 
 
+VQ_MAX_CODES = 256  # codewords of one codebook at most (csrc/vq.hip stages a codebook into 16 KiB of LDS)
+
+_VQ_SHAPE = "unsupported VQ shape (1 <= F <= 8, 1 <= T <= 1024, 1 <= Kmax <= %d)" % VQ_MAX_CODES
+
+
+def _vq_book_args(cb, n_codes, F, device):
+    """(cb float64 [C, Kmax, F], n_codes int32 [C]) on the device and their C-ABI arguments."""
+    import torch
+    cb = _as_device(cb, torch.float64, device)
+    n_codes = _as_device(n_codes, torch.int32, device).reshape(-1)
+    if cb.dim() != 3 or n_codes.numel() != cb.shape[0]:
+        raise ValueError("codebooks must be [C, Kmax, F] with one n_codes per codebook")
+    if cb.shape[2] != F:
+        raise ValueError("sequences of %d feature channels against codebooks of %d" % (F, cb.shape[2]))
+    return cb, n_codes, [_hip.ptr(cb), _hip.ptr(n_codes), cb.shape[0], cb.shape[1]]
+
+
+def vq_score(cb, n_codes, seqs, lengths, with_labels=False, check_finite=True):
+    """Total quantisation distortions (include/dsp_audiorec.h: dsp_vq_score) of the padded sequences
+    [N, T, F] under every codebook of cb [C, Kmax, F] with n_codes [C]: (score float64 [N, C], the sum over
+    the sequence's frames of the squared distance to the nearest codeword; label int32 [N] or None: the
+    smallest score's codebook, -1 when every score is +inf) on the device."""
+    import torch
+    d = _hip.require_device()
+    x, n = _dtw_operand(seqs, lengths, d, check_finite)
+    N, T, F = x.shape
+    cb, n_codes, bargs = _vq_book_args(cb, n_codes, F, d)
+    C, Kmax = bargs[-2:]
+    score = torch.empty((N, C), dtype=torch.float64, device=d)
+    label = torch.empty(N, dtype=torch.int32, device=d) if with_labels else None
+    if N > 0:
+        ws = _grown(None, _hip.lib().dsp_vq_workspace_bytes(C, N, 0, T, F, Kmax), _VQ_SHAPE, d)
+        rc = _hip.lib().dsp_vq_score(*bargs, _hip.ptr(x), _hip.ptr(n), N, T, F, _hip.ptr(score), _hip.ptr(label),
+                                     _hip.ptr(ws), ws.numel(), _hip.stream_handle(d))
+        _hip.check(rc, "dsp_vq_score")
+    return score, label
+
+
+class VqUpdater(_PairListPlan):
+    """The sequences of an LBG training run uploaded once with their CSR class lists (one group per
+    codebook); the workspace is held across rounds.  ``assign`` is one ``dsp_vq_assign`` call for all
+    codebooks, ``accumulate`` one ``dsp_vq_accumulate`` call."""
+
+    def _workspace(self, Kmax):
+        return self._grow(_hip.lib().dsp_vq_workspace_bytes(self.C, self.N, self.P, self.T, self.F, Kmax), _VQ_SHAPE)
+
+    def assign(self, cb, n_codes, with_codes=True):
+        """(dist float64 [P], code int32 [P, T] or None) of every listed pair."""
+        import torch
+        d = self.device
+        cb, n_codes, bargs = _vq_book_args(cb, n_codes, self.F, d)
+        C, Kmax = bargs[-2:]
+        if C != self.C:
+            raise ValueError("%d codebooks for %d groups" % (C, self.C))
+        dist = torch.empty(self.P, dtype=torch.float64, device=d)
+        code = torch.empty((self.P, self.T), dtype=torch.int32, device=d) if with_codes else None
+        if self.P > 0 and C > 0:
+            ws = self._workspace(Kmax)
+            rc = _hip.lib().dsp_vq_assign(*bargs, _hip.ptr(self.seqs), _hip.ptr(self.len_s), self.N, self.T, self.F,
+                                          _hip.ptr(self.start), _hip.ptr(self.members), self.P, _hip.ptr(dist),
+                                          _hip.ptr(code), _hip.ptr(ws), ws.numel(), _hip.stream_handle(d))
+            _hip.check(rc, "dsp_vq_assign")
+        return dist, code
+
+    def accumulate(self, cb_prev, n_codes, code, dist):
+        """The Lloyd re-estimation from given codes: (centroid float64 [C, Kmax, F], cnt int32 [C, Kmax],
+        n_valid int32 [C], total float64 [C]) on the device."""
+        import torch
+        d = self.device
+        cb_prev, n_codes, bargs = _vq_book_args(cb_prev, n_codes, self.F, d)
+        C, Kmax = bargs[-2:]
+        code = _as_device(code, torch.int32, d)
+        dist = _as_device(dist, torch.float64, d).reshape(-1)
+        if C != self.C or tuple(code.shape) != (self.P, self.T) or dist.numel() != self.P:
+            raise ValueError("codebooks [%d, %d, %d], code %s for %d groups, %d pairs of %d frames"
+                             % (C, Kmax, self.F, tuple(code.shape), self.C, self.P, self.T))
+        centroid = torch.empty_like(cb_prev)
+        cnt = torch.empty((C, Kmax), dtype=torch.int32, device=d)
+        n_valid = torch.empty(C, dtype=torch.int32, device=d)
+        total = torch.empty(C, dtype=torch.float64, device=d)
+        if C > 0:
+            ws = self._workspace(Kmax)
+            rc = _hip.lib().dsp_vq_accumulate(*bargs, _hip.ptr(self.seqs), _hip.ptr(self.len_s), self.N, self.T, self.F,
+                                              _hip.ptr(self.start), _hip.ptr(self.members), self.P, _hip.ptr(code),
+                                              _hip.ptr(dist), _hip.ptr(centroid), _hip.ptr(cnt), _hip.ptr(n_valid),
+                                              _hip.ptr(total), _hip.ptr(ws), ws.numel(), _hip.stream_handle(d))
+            _hip.check(rc, "dsp_vq_accumulate")
+        return centroid, cnt, n_valid, total
+
+
+def vq_assign(cb, n_codes, seqs, lengths, groups=None, assign=None, with_codes=True, check_finite=True):
+    """Nearest codewords (include/dsp_audiorec.h: dsp_vq_assign) of the frames of the padded sequences
+    seqs[members[p]] under codebook c, the pairs given as the CSR ``groups=(group_start [C + 1], members
+    [P])`` or as ``assign`` [N] (the codebook of each sequence, -1 to skip).  Returns (dist float64 [P],
+    code int32 [P, T] or None, group_start, members) on the device: code[p, t] is the codeword of frame t
+    (-1 behind the sequence's frames, and everywhere for an invalid pair)."""
+    N = len(lengths)
+    start, members = _dtw_groups(groups, assign, len(_as_host(n_codes).reshape(-1)), N)
+    up = VqUpdater(seqs, lengths, start, members, check_finite)
+    dist, code = up.assign(cb, n_codes, with_codes)
+    return dist, code, up.start, up.members
+
+
+def vq_split(cb, eps):
+    """The binary split of LBG training on cb [..., K, F] -> [..., 2 K, F]: codeword j becomes
+    2 j = c + eps and 2 j + 1 = c - eps, elementwise (one rounded fp64 add / subtract each)."""
+    cb = _as_host(cb, np.float64)
+    eps = np.float64(eps)
+    out = np.empty(cb.shape[:-2] + (2 * cb.shape[-2], cb.shape[-1]))
+    out[..., 0::2, :] = cb + eps
+    out[..., 1::2, :] = cb - eps
+    return out
+
+
+def vq_repair_empty(cb, cnt, n_codes, eps):
+    """The empty-cell rule of LBG training on cb [C, Kmax, F] with the frame counts cnt [C, Kmax] of the
+    round that produced it -> (cb, cnt) copies with, for each codebook and each empty cell j (cnt == 0,
+    j < n_codes[c]) in ascending order: the donor is the cell with the largest cnt >= 2, ties to the
+    smaller index; cb[j] = cb[donor] + eps, then cb[donor] = cb[donor] - eps, elementwise; for the rest of
+    the pass the donor keeps cnt - cnt // 2 and j gets cnt // 2.  Without a donor the cell is left as it
+    is."""
+    cb = np.array(_as_host(cb, np.float64))
+    cnt = np.array(_as_host(cnt)).astype(np.int64)
+    n_codes = _as_host(n_codes).astype(np.int64).reshape(-1)
+    eps = np.float64(eps)
+    for c in range(cb.shape[0]):
+        K = int(n_codes[c])
+        for j in range(K):
+            if cnt[c, j] != 0:
+                continue
+            donor = int(np.argmax(cnt[c, :K]))  # the first of the largest
+            if cnt[c, donor] < 2:
+                continue
+            cb[c, j] = cb[c, donor] + eps
+            cb[c, donor] = cb[c, donor] - eps
+            cnt[c, j] = cnt[c, donor] // 2
+            cnt[c, donor] -= cnt[c, j]
+    return cb, cnt
+
+
 class _CropFramePlan:
     """What the launch plans of the two crop-frame kernels (csrc/crop_frames.h) share: ``PitchTracker`` and
     ``LpcAnalyzer`` run after a ``FeatureExtractor`` call, on that call's device outputs, and validate

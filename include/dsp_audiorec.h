@@ -36,7 +36,7 @@ extern "C" {
                               5: queue_ws is 4 KiB (each counter on its own 256-B line);
                               6: the extraction entry points take out_stride (packed result rows);
                                  dsp_knn_classify takes flags (DSP_KNN_REF_READY).
-                              Still 6 with the dsp_mlp_*, dsp_svc_*, dsp_gnb_*, dsp_tree_* and dsp_dtw_* (dsp_dtw_align, dsp_dtw_dba_update included) and dsp_hmm_* and dsp_pitch_* and dsp_lpc_* entry points: new symbols only, no
+                              Still 6 with the dsp_mlp_*, dsp_svc_*, dsp_gnb_*, dsp_tree_* and dsp_dtw_* (dsp_dtw_align, dsp_dtw_dba_update included) and dsp_hmm_* and dsp_vq_* and dsp_pitch_* and dsp_lpc_* entry points: new symbols only, no
                               existing signature or meaning changed, so callers built against 6 keep
                               working (a binding that needs them checks for the symbols) */
 
@@ -578,6 +578,78 @@ int dsp_hmm_accumulate(const double *mu_prev, const double *var_prev, const int3
                        const int32_t *group_start, const int32_t *members, int64_t P, const int32_t *seg,
                        const double *score, double var_floor, double *mean, double *var, int32_t *cnt,
                        int32_t *n_valid, double *total, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Vector-quantisation codebooks on the frame sequences: the nearest codeword of every frame, the total
+ * distortion of a sequence under a codebook, and one Lloyd re-estimation -- the pieces of LBG training
+ * and of the VQ word recogniser (one codebook per word, the label of the smallest distortion).
+ * csrc/vq.hip, DESIGN.md §4.13.  Every output is defined bit for bit: the device computes fp64 subtract,
+ * multiply, add, compare and (in the re-estimation) one divide in the order below, each operation
+ * rounded, no FMA; there is no certificate and no math library.
+ *
+ * Sequences: x float64 [N, T, F] padded row-major with len int32 [N], 1 <= F <= 8, 1 <= T <= 1024 (the
+ *   DTW plan above).
+ * Codebook set: C <= 2^20 codebooks padded to Kmax <= 256 codewords: cb float64 [C, Kmax, F], n_codes
+ *   int32 [C], 1 <= n_codes[c] <= Kmax.  Frames and codewords are finite; for other values the results
+ *   are unspecified, but nothing is read or written out of bounds.  Rows k >= n_codes[c] are never read
+ *   by the search.
+ * For frame t of a sequence of n frames and a codebook of K codewords:
+ *     d(t,k) = e0 * e0, then for f = 1 .. F-1 ascending:  e = x[t,f] - cb[k,f];  d = d + e * e
+ *                                                         (e0 = x[t,0] - cb[k,0])
+ *     best = d(t,0), code = 0;  for k = 1 .. K-1 ascending:  if d(t,k) < best (strictly): best = d(t,k), code = k
+ *     D = best(0);  D = D + best(t)  for t = 1 .. n-1 ascending
+ *   Ties go to the smaller codeword index; D is the sequence's total distortion.  D is +inf, and every
+ *   code -1, when n < 1, n > T, n_codes[c] is outside 1 .. Kmax, or a list entry is outside [0, N);
+ *   nothing of such a member is read through.  A distance that overflows is +inf; if all overflow the
+ *   code is 0.
+ * Pairs (dsp_vq_assign, dsp_vq_accumulate): dsp_dtw_align's CSR list over the codebooks -- group_start
+ *   int32 [C + 1], members int32 [P]; a sequence may appear under several codebooks and several times
+ *   under one; a group may be empty.
+ *
+ * dsp_vq_score: every sequence against every codebook, score float64 [N, C] (= D); label int32 [N] the
+ *   codebook of the smallest D, ties to the smaller index, -1 when every D is +inf.  Either output may
+ *   be NULL.
+ * dsp_vq_assign: dist float64 [P] (= D) and code int32 [P, T] of the listed pairs: code[p, t] is the
+ *   frame's codeword, -1 for t >= n and everywhere for an invalid pair.  Either may be NULL (without
+ *   code nothing per frame is stored).
+ * dsp_vq_accumulate: one Lloyd re-estimation of every codebook from a GIVEN code [P, T] and dist [P]
+ *   (the output of dsp_vq_assign, or the caller's own, e.g. all zeros for the one-codeword start).  A
+ *   member is valid when its index and length are and every code[p, t], t < n, lies in [0, n_codes[c]);
+ *   other members are skipped and nothing of their frames is read.  For codebook c with valid members
+ *   k0 < k1 < ... in list order:
+ *     m_k[j]    = number of the member's frames with code j
+ *     X_k[j,f]  = the member's frames with code j added left to right (t ascending; the first is the
+ *                 value itself)
+ *     accX[j,f] = X_k of the first member with m_k[j] > 0, then accX + X_k for each later member with
+ *                 m_k[j] > 0, in list order (a member with m_k[j] = 0 adds nothing to cell j -- not even
+ *                 0.0, so a cell of -0.0 frames stays -0.0)
+ *     cnt[j]    = sum_k m_k[j]                          integer
+ *     centroid[j,f] = accX[j,f] / (double) cnt[j] where cnt[j] > 0;  cb_prev[c,j,f] bit for bit where not
+ *     total[c]  = dist_k0 + dist_k1 + ...               in list order;  n_valid[c] = number of valid members
+ *   Outputs centroid float64 [C, Kmax, F] (may not be cb_prev), cnt int32 [C, Kmax], n_valid int32 [C],
+ *   total float64 [C].  Rows j >= K are zeros.  A codebook with no valid member or an n_codes outside
+ *   1 .. Kmax is copied bit for bit from cb_prev (all Kmax rows), with total 0.0, n_valid 0 and cnt 0.
+ * workspace  device scratch of dsp_vq_workspace_bytes(C, N, P, T, F, Kmax) bytes (0: sizes outside the
+ *   plan; P = 0 for dsp_vq_score): N x C scores (labels without scores), and for the re-estimation the
+ *   sums, counts and validity of one chunk of pairs (at most 128 MiB) and the codebooks' counts.
+ *   Nothing in it is carried from one call to the next.
+ * All three check their host arguments before any launch (DSP_ERR_ARGS, DSP_ERR_WORKSPACE), return
+ * DSP_OK with nothing to do, make no host synchronisation and no allocation, and write only to their
+ * outputs and the workspace, on the caller's stream.
+ */
+size_t dsp_vq_workspace_bytes(int64_t C, int64_t N, int64_t P, int T, int F, int Kmax);
+int dsp_vq_score(const double *cb, const int32_t *n_codes, int64_t C, int Kmax, const double *x,
+                 const int32_t *len, int64_t N, int T, int F, double *score, int32_t *label, void *workspace,
+                 size_t workspace_bytes, void *stream);
+int dsp_vq_assign(const double *cb, const int32_t *n_codes, int64_t C, int Kmax, const double *x,
+                  const int32_t *len, int64_t N, int T, int F, const int32_t *group_start,
+                  const int32_t *members, int64_t P, double *dist, int32_t *code, void *workspace,
+                  size_t workspace_bytes, void *stream);
+int dsp_vq_accumulate(const double *cb_prev, const int32_t *n_codes, int64_t C, int Kmax, const double *x,
+                      const int32_t *len, int64_t N, int T, int F, const int32_t *group_start,
+                      const int32_t *members, int64_t P, const int32_t *code, const double *dist,
+                      double *centroid, int32_t *cnt, int32_t *n_valid, double *total, void *workspace,
+                      size_t workspace_bytes, void *stream);
 
 /*
  * Short-time autocorrelation pitch track -- the fourth classical time-domain feature next to energy,
