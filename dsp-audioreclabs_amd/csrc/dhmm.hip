@@ -1,0 +1,472 @@
+// dhmm.hip -- left-to-right hidden Markov models with DISCRETE observations (a symbol per frame, the
+// output of a shared VQ codebook), in the negative-log domain, on gfx950 (include/dsp_audiorec.h:
+// dsp_dhmm_score, dsp_dhmm_align, dsp_dhmm_accumulate).  An extension like §4.8-§4.13:
+// nothing here restates a reference file.  Every value is defined bit for bit: the device sees only
+// fp64 add and min and integer counts; the logarithms are taken on the host when the model is built.
+//
+// Symbols.  sym int32 [N, T] padded row-major with len int32 [N], 1 <= T <= 1024: the layout of
+// dsp_vq_assign's code for members = 0 .. N-1 of one group.  Entries at t >= len are never read through.
+// Alphabet.  K symbols, 1 <= K <= 256, shared by all models of a set.
+// Model set.  C models padded to Smax <= 32 states, 1 <= n_states[c] <= Smax: emit float64 [C, Smax, K]
+// (= -log b_s(k)), stay, adv float64 [C, Smax], all finite or +inf, never NaN, never -inf; adv[c, S-1]
+// and the rows s >= S are never read.
+// Recurrence, for a sequence of length n and a model of S states (fp64 add and min only, each rounded):
+//   e(t,s)  = emit[c, s, sym[t]]
+//   V(0,0)  = e(0,0);  V(0,s>0) = +inf
+//   a = V(t-1,s) + stay[s];  b = V(t-1,s-1) + adv[s-1]   (b = +inf at s = 0)
+//   V(t,s)  = e(t,s) + min(a, b)
+//   score   = V(n-1, S-1)
+// The score is +inf when n < S (it comes out of the recurrence), when n < 1 or n > T, when n_states is
+// outside 1 .. Smax, for a list entry outside [0, N), and when any sym[t], t < n, lies outside [0, K):
+// such a symbol never indexes the table (the index is clamped and the result forced).
+// Path.  hmm.hip's, word for word: walk back from (n-1, S-1), the predecessor is the advance iff b < a
+// strictly; seg int32 [P, Smax], seg[s] the first frame of state s, -1 behind the model's states and
+// everywhere for a pair whose score is +inf.
+// Re-estimation from a GIVEN seg [P, Smax] and score [P]: a member is valid when its index and length
+// are, its seg row is well formed for its model (seg[0] = 0, strictly increasing over the S states,
+// seg[S-1] < n) and every sym[t], t < n, lies in [0, K); any other member is skipped whole.
+//   cnt_emit[c,s,k] = frames of valid members in state s that carry symbol k;  cnt[c,s] likewise over all k
+//   n_valid[c] = valid members;  total[c] = their scores added in list order, the first the value itself
+// Rows s >= S are zeros; a model without a valid member or with an invalid n_states has all-zero counts,
+// total 0.0 and n_valid 0.  The counts are integers, so the order the device adds them in is free.
+//
+// Kernels:
+//   dhmm_pack   the set as one record per model in the workspace, END-aligned to NS register slots
+//              (NS = 8, 16 or 32, the smallest that holds Smax): state s of a model of S states sits in
+//              slot s + NS - S, so the result is always slot NS - 1; the leading slots hold zeros (their
+//              cells start at +inf and stay there).  A record is the emission table transposed to
+//              [K][NS] -- one symbol's slots contiguous -- and then (stay, adv[s-1]) per slot.
+//   dhmm_dp<NS, DIR>  hmm_dp's shape: one persistent wave per tile of ONE model and 64 sequences, a lane
+//              per sequence, the tiles from csr_pairs.h's csr_walk; the NS cells of a lane in registers,
+//              the state loop fully unrolled, slots swept in descending order in place; the lane's
+//              symbol one row ahead through the vector path.  The record is staged into LDS when the
+//              tile's model is not the one staged last: symbol k's slots at byte k * (8 NS + 16), the
+//              16 bytes of padding making the pitch an odd number of 16-byte units, so symbols k and k'
+//              share a bank window only when k = k' (mod 16) -- and then broadcast if k = k'.  A row
+//              is NS / 2 ds_read_b128 of the lane's own symbol's slots (a true gather, two states per
+//              read) and NS broadcast ds_read_b128 of (stay, adv[s-1]); no scalar load in the loop,
+//              so the waits are counted lgkmcnt.  4 fp64 instructions per cell; DIR as hmm_dp's.
+//   csr_label  (csr_pairs.h) the label of a score matrix.
+//   dhmm_pairs / dhmm_count / dhmm_totals   the re-estimation: a thread per pair (its model by bisection
+//              of group_start, the seg row and symbol range checks), a thread per (pair, frame) (the
+//              frame's state from the seg row, vector atomic adds on the int32 counts), a thread per
+//              model (the ordered total and n_valid); csr_zero_counts zeroes the counts first.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+
+#include "csr_pairs.h"
+#include "dsp_audiorec.h"
+#include "dtw_internal.h"
+
+namespace dsp {
+
+static constexpr int DHMM_SMAX = 32;                 // states a lane keeps in registers at most
+static constexpr int DHMM_KMAX = 256;                // symbols of the alphabet at most
+static constexpr int64_t DHMM_CMAX = 1 << 20;        // models in a set at most
+static constexpr int DHMM_GCHUNK = 1024;             // models per launch at most
+static constexpr size_t DHMM_WAVE_CAP = 256u << 20;  // bytes of direction words per launch
+static constexpr int DHMM_BATCH = 16;                // members whose loads a totals thread keeps in flight
+
+// register slots of a launch: the smallest of 8, 16, 32 that holds Smax
+static inline int dhmm_slots(int Smax) { return Smax <= 8 ? 8 : (Smax <= 16 ? 16 : 32); }
+// doubles of one model's record: [K][NS] emissions, then [NS][2] (stay, adv[s-1])
+static inline size_t dhmm_record(int K, int NS) { return (size_t)K * NS + 2 * (size_t)NS; }
+// bytes between two symbols' slots in LDS: an odd number of 16-byte units (NS is a multiple of 4)
+__host__ __device__ static inline int dhmm_pitch(int NS) { return NS * 8 + 16; }
+static inline size_t dhmm_lds_bytes(int K, int NS) { return (size_t)K * dhmm_pitch(NS) + (size_t)NS * 16; }
+
+// rec [C][K * NS + 2 NS], see above; a model with an invalid n_states gets zeros (never read)
+__global__ __launch_bounds__(256) void dhmm_pack(const double *__restrict__ emit, const double *__restrict__ stay,
+                                                 const double *__restrict__ adv, const int32_t *__restrict__ n_states,
+                                                 int64_t C, int Smax, int K, int NS, double *__restrict__ rec)
+{
+    const int64_t R = (int64_t)K * NS + 2 * NS, total = C * R;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+        const int64_t c = e / R;
+        const int r = (int)(e % R);
+        const bool tab = r < K * NS;
+        const int j = tab ? r % NS : (r - K * NS) / 2;
+        const int S = n_states[c], s = j - (NS - S);
+        double v = 0.0;
+        if (S >= 1 && S <= Smax && s >= 0) {
+            const int64_t cs = c * Smax + s;
+            if (tab)
+                v = emit[cs * K + r / NS];
+            else if ((r - K * NS) % 2 == 0)
+                v = stay[cs];
+            else
+                v = s > 0 ? adv[cs - 1] : 0.0;
+        }
+        rec[e] = v;
+    }
+}
+
+#pragma clang fp contract(off)
+// One row of the NS slots: v holds row t-1 and is replaced by row t; erow: the slots of the lane's own
+// symbol in LDS; tr: (stay, adv[s-1]) per slot in LDS, the same address for every lane.  FIRST: row 0,
+// slot j0 (state 0) starts the path.  DIR: bit j of word = "the predecessor of slot j is the advance".
+template <int NS, bool FIRST, bool DIR>
+__device__ __forceinline__ void dhmm_row(double (&v)[NS], const double2 *erow, const double2 *tr, int j0, uint32_t &word)
+{
+    uint32_t md = 0;
+    double2 e2[NS / 2];
+    // the row's gather is issued before its cells: NS / 2 reads in flight, consumed in descending order
+#pragma unroll
+    for (int i = NS / 2 - 1; i >= 0; i--) e2[i] = erow[i];
+    // slots in descending order: slot j reads row t-1 of slots j and j-1 only, so it is replaced in place
+#pragma unroll
+    for (int j = NS - 1; j >= 0; j--) {
+        const double e = (j & 1) ? e2[j / 2].y : e2[j / 2].x;
+        if (FIRST) {
+            v[j] = j == j0 ? e : (double)INFINITY;
+        } else {
+            const double2 sa = tr[j];
+            const double a = v[j] + sa.x;
+            const double b = (j > 0 ? v[j - 1] : (double)INFINITY) + sa.y;
+            // md = 2 md + (b < a): the compare's bit shifted in through the carry
+            if (DIR)
+                asm("v_cmp_lt_f64 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(md) : "v"(b), "v"(a) : "vcc");
+            v[j] = e + dtw_min(a, b);
+        }
+    }
+    if (DIR) word = md;
+}
+
+// V(n-1, S-1) of the lane's symbol row sr (n its length, 0: nothing of the lane is used) under the model
+// staged in LDS (tab: its table, tr: its transitions), state 0 in slot j0; nmax > 0 the wave's largest n.
+// A symbol outside [0, K) at t < n forces +inf; its index is clamped.  dir: this wave's direction words
+// at this lane, [row][lane]; NULL: not stored.
+template <int NS, bool DIR>
+__device__ __forceinline__ double dhmm_sweep(const unsigned char *tab, const double2 *tr, int j0, int K,
+                                             const int32_t *__restrict__ sr, int n, int nmax, uint32_t *dir)
+{
+    constexpr int PITCH = NS * 8 + 16;
+    double v[NS];
+    uint32_t word = 0;
+    auto row_of = [&](int k) { return (const double2 *)(tab + (unsigned)min((unsigned)k, (unsigned)(K - 1)) * PITCH); };
+    int k = sr[0];
+    bool bad = n >= 1 && (unsigned)k >= (unsigned)K;
+    dhmm_row<NS, true, DIR>(v, row_of(k), tr, j0, word);
+    if (DIR && dir) dir[0] = 0;
+    double res = n == 1 ? v[NS - 1] : (double)INFINITY;
+    k = sr[min(1, nmax - 1)];
+    for (int t = 1; t < nmax; t++) {
+        const int kn = sr[min(t + 1, nmax - 1)];  // the next row's symbol, asked for before this row's cells
+        bad = bad || (t < n && (unsigned)k >= (unsigned)K);
+        dhmm_row<NS, false, DIR>(v, row_of(k), tr, j0, word);
+        if (DIR && dir) dir[(size_t)t * 64] = word;
+        if (t == n - 1) res = v[NS - 1];
+        k = kn;
+    }
+    return bad ? (double)INFINITY : res;
+}
+#pragma clang fp contract(on)
+
+// The models c = 0 .. nc-1 of this launch (rec, n_states and group_start already point at the first
+// one, model c0 of the set).  group_start == NULL: every model against all N sequences, the result
+// of (sequence r, model c) at score[r * C + c0 + c]; else the CSR pairs, outputs indexed by p.
+// Dynamic LDS: K * (8 NS + 16) + 16 NS bytes.  At 32 slots the LDS lets about two waves per SIMD stay
+// resident anyway (K = 64: nine tables per CU), so the scheduler is told to plan for two: with the
+// registers that frees it keeps up to 14 transition reads in flight instead of one.
+template <int NS, bool DIR>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, NS == 32 ? 2 : 8))) void dhmm_dp(const double *__restrict__ rec, const int32_t *__restrict__ n_states, int c0,
+                                              int nc, int64_t C, int Smax, int K, const int32_t *__restrict__ sym,
+                                              const int32_t *__restrict__ len, int64_t N, int T,
+                                              const int32_t *__restrict__ group_start,
+                                              const int32_t *__restrict__ members, int P, double *__restrict__ score,
+                                              int32_t *__restrict__ seg, uint32_t *dir_ws)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char dhmm_lds[];
+    constexpr int PITCH = NS * 8 + 16;
+    const int lane = (int)threadIdx.x, wv = (int)blockIdx.x;
+    const size_t R = (size_t)K * NS + 2 * NS;
+    const double2 *tr = (const double2 *)(dhmm_lds + (size_t)K * PITCH);
+    uint32_t *dir = DIR && seg ? dir_ws + (size_t)wv * (size_t)T * 64 + lane : nullptr;
+    int staged = -1;
+    csr_walk((int)gridDim.x, wv, nc, group_start, 0, group_start ? P : (int)N, members, len, N, T,
+             [&](int cg, const CsrLane &ln) {
+                 const int S = n_states[cg], n = ln.len;
+                 const bool sok = S >= 1 && S <= Smax;
+                 const int64_t p = ln.p;
+                 double res = INFINITY;
+                 if (sok && ln.lmax > 0) {
+                     if (staged != cg) {
+                         // 16-byte pieces of the record: K * NS / 2 of the table, then NS of the transitions
+                         const double2 *__restrict__ src = (const double2 *)(rec + (size_t)cg * R);
+                         const int ne = K * (NS / 2);
+                         __syncthreads();  // one wave: the reads of the table staged before are done
+                         for (int i = lane; i < ne + NS; i += 64) {
+                             const int kk = i / (NS / 2), jj = i % (NS / 2);
+                             const size_t at = i < ne ? (size_t)kk * PITCH + (size_t)jj * 16
+                                                      : (size_t)K * PITCH + (size_t)(i - ne) * 16;
+                             *(double2 *)(dhmm_lds + at) = src[i];
+                         }
+                         __syncthreads();
+                         staged = cg;
+                     }
+                     res = dhmm_sweep<NS, DIR>(dhmm_lds, tr, NS - S, K, sym + (int64_t)ln.row * T, n, ln.lmax, dir);
+                 }
+                 if (!ln.inr) return;
+                 if (score) score[group_start ? p : p * C + c0 + cg] = res;
+                 if (!DIR || !seg) return;
+                 int32_t *__restrict__ ps = seg + p * Smax;
+                 int filled = 0;
+                 if (res < INFINITY) {
+                     // the lane's own walk back: state s is slot s + NS - S, that bit of a row's word
+                     int s = S - 1;
+                     for (int r = n - 1; r >= 1 && s > 0; r--)
+                         if ((dir[(size_t)r * 64] >> (s + NS - S)) & 1) ps[s--] = r;
+                     for (; s > 0; s--) ps[s] = s;  // not reached with the sweep's own words
+                     ps[0] = 0;
+                     filled = S;
+                 }
+                 for (int i = filled; i < Smax; i++) ps[i] = -1;
+             });
+}
+
+// ---- re-estimation ----
+// A thread per pair: pmodel[p] = its model (the group that holds p, by bisection of group_start) when
+// the member is valid, else -1.
+__global__ __launch_bounds__(256) void dhmm_pairs(const int32_t *__restrict__ n_states, int64_t C, int Smax, int K,
+                                                  const int32_t *__restrict__ sym, const int32_t *__restrict__ len,
+                                                  int64_t N, int T, const int32_t *__restrict__ group_start,
+                                                  const int32_t *__restrict__ members, int64_t P,
+                                                  const int32_t *__restrict__ seg, int32_t *__restrict__ pmodel)
+{
+    for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < P; p += (int64_t)gridDim.x * 256) {
+        int64_t lo = 0, hi = C;  // the last c with group_start[c] <= p
+        while (hi - lo > 1) {
+            const int64_t mid = (lo + hi) / 2;
+            if (group_start[mid] <= p)
+                lo = mid;
+            else
+                hi = mid;
+        }
+        const int S = n_states[lo], mem = members[p];
+        const int32_t *__restrict__ ps = seg + p * Smax;
+        bool ok = S >= 1 && S <= Smax && mem >= 0 && mem < N && p >= group_start[lo] && p < group_start[lo + 1];
+        const int n = ok ? len[mem] : 0;
+        ok = ok && n >= 1 && n <= T && ps[0] == 0;
+        for (int s = 0; ok && s < S; s++) {
+            const int b = ps[s], e = s + 1 < S ? ps[s + 1] : n;
+            ok = b >= 0 && b < e && e <= n;
+        }
+        if (ok) {
+            const int32_t *__restrict__ sr = sym + (int64_t)mem * T;
+            unsigned worst = 0;
+            for (int t = 0; t < n; t++) worst = max(worst, (unsigned)sr[t]);
+            ok = worst < (unsigned)K;
+        }
+        pmodel[p] = ok ? (int32_t)lo : -1;
+    }
+}
+
+// A thread per (pair, frame): the frame's state from the seg row; one atomic add per frame on cnt_emit
+// and one per (pair, state) on cnt (the state's first frame adds its length).
+__global__ __launch_bounds__(256) void dhmm_count(const int32_t *__restrict__ n_states, int Smax, int K,
+                                                  const int32_t *__restrict__ sym, const int32_t *__restrict__ len, int T,
+                                                  const int32_t *__restrict__ members, int64_t P,
+                                                  const int32_t *__restrict__ seg, const int32_t *__restrict__ pmodel,
+                                                  int32_t *__restrict__ cnt_emit, int32_t *__restrict__ cnt)
+{
+    const int64_t total = P * T;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+        const int64_t p = e / T;
+        const int t = (int)(e % T), c = pmodel[p];
+        if (c < 0) continue;
+        const int mem = members[p], n = len[mem];
+        if (t >= n) continue;
+        const int S = n_states[c];
+        const int32_t *__restrict__ ps = seg + p * Smax;
+        int s = 0;
+        while (s + 1 < S && ps[s + 1] <= t) s++;
+        const int64_t cs = (int64_t)c * Smax + s;
+        atomicAdd(&cnt_emit[cs * K + sym[(int64_t)mem * T + t]], 1);
+        if (t == ps[s]) atomicAdd(&cnt[cs], (s + 1 < S ? ps[s + 1] : n) - t);
+    }
+}
+
+#pragma clang fp contract(off)
+// A thread per model: n_valid and total, the valid members' scores added in list order
+__global__ __launch_bounds__(256) void dhmm_totals(int64_t C, const int32_t *__restrict__ group_start, int64_t P,
+                                                   const int32_t *__restrict__ pmodel, const double *__restrict__ score,
+                                                   int32_t *__restrict__ n_valid, double *__restrict__ total_out)
+{
+    for (int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x; c < C; c += (int64_t)gridDim.x * 256) {
+        const int g0 = clampi(group_start[c], 0, (int)P), g1 = clampi(group_start[c + 1], 0, (int)P);
+        int nv = 0;
+        double tot = 0.0;
+        for (int p0 = g0; p0 < g1; p0 += DHMM_BATCH) {
+            bool ok[DHMM_BATCH];
+            double sc[DHMM_BATCH];
+#pragma unroll
+            for (int u = 0; u < DHMM_BATCH; u++) {
+                const bool in_group = p0 + u < g1;
+                ok[u] = in_group && pmodel[p0 + u] == c;
+                sc[u] = in_group ? score[p0 + u] : 0.0;
+            }
+#pragma unroll
+            for (int u = 0; u < DHMM_BATCH; u++) {
+                if (!ok[u]) continue;
+                tot = nv == 0 ? sc[u] : tot + sc[u];
+                nv++;
+            }
+        }
+        n_valid[c] = nv;
+        total_out[c] = tot;
+    }
+}
+#pragma clang fp contract(on)
+
+// ---- host side ----
+static bool dhmm_in_plan(int64_t C, int64_t N, int64_t P, int T, int Smax, int K)
+{
+    return C >= 0 && C <= DHMM_CMAX && N >= 0 && N < 0x7fffffff && P >= 0 && P < 0x7fffffff && Smax >= 1 &&
+           Smax <= DHMM_SMAX && K >= 1 && K <= DHMM_KMAX && T >= 1 && T <= DTW_TMAX;
+}
+
+// workspace: [records of the C models][direction words of G waves][score [N, C], for labels without
+// scores][the pairs' models: dsp_dhmm_accumulate]
+struct DhmmPlan {
+    int NS, G;
+    size_t rec, dir, score, pmodel;
+    size_t total() const { return rec + dir + score + pmodel; }
+};
+static int dhmm_waves(int64_t tiles, int T, bool with_dir)
+{
+    const int64_t cap = with_dir ? std::max<int64_t>(1, (int64_t)(DHMM_WAVE_CAP / ((size_t)T * 64 * 4))) : DTW_WAVES;
+    return (int)std::max<int64_t>(1, std::min<int64_t>(tiles, std::min<int64_t>(DTW_WAVES, cap)));
+}
+static DhmmPlan dhmm_plan(int64_t C, int64_t N, int64_t P, int T, int Smax, int K)
+{
+    DhmmPlan pl;
+    pl.NS = dhmm_slots(Smax);
+    pl.G = dhmm_waves(P / 64 + std::min<int64_t>(C, DHMM_GCHUNK), T, true);
+    pl.rec = up256((size_t)C * dhmm_record(K, pl.NS) * 8);
+    pl.dir = up256((size_t)pl.G * T * 64 * 4);
+    pl.score = up256((size_t)N * C * 8);
+    pl.pmodel = up256((size_t)P * 4);
+    return pl;
+}
+
+template <int NS, bool DIR>
+static hipError_t dhmm_launch(dim3 grid, size_t lds, hipStream_t s, const double *rec, const int32_t *n_states, int c0,
+                              int nc, int64_t C, int Smax, int K, const int32_t *sym, const int32_t *len, int64_t N, int T,
+                              const int32_t *group_start, const int32_t *members, int P, double *score, int32_t *seg,
+                              uint32_t *dir)
+{
+    if (lds > 65536) {  // K = 256 at 32 slots: past the default limit of dynamic LDS
+        const hipError_t e = hipFuncSetAttribute((const void *)dhmm_dp<NS, DIR>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL((dhmm_dp<NS, DIR>), grid, dim3(64), lds, s, rec, n_states, c0, nc, C, Smax, K, sym, len, N, T,
+                       group_start, members, P, score, seg, dir);
+    return hipSuccess;
+}
+
+// the records, then the DP over all models in launches of at most DHMM_GCHUNK
+template <bool DIR>
+static int dhmm_run(hipStream_t s, const DhmmPlan &pl, void *ws, const double *emit, const double *stay, const double *adv,
+                    const int32_t *n_states, int64_t C, int Smax, int K, const int32_t *sym, const int32_t *len, int64_t N,
+                    int T, const int32_t *group_start, const int32_t *members, int64_t P, double *score, int32_t *seg)
+{
+    double *rec = (double *)ws;
+    uint32_t *dir = (uint32_t *)((char *)ws + pl.rec);
+    const int NS = pl.NS;
+    const size_t R = dhmm_record(K, NS), lds = dhmm_lds_bytes(K, NS);
+    hipLaunchKernelGGL(dhmm_pack, csr_grid(C * (int64_t)R), dim3(256), 0, s, emit, stay, adv, n_states, C, Smax, K, NS, rec);
+    for (int64_t c0 = 0; c0 < C; c0 += DHMM_GCHUNK) {
+        const int64_t nc = std::min<int64_t>(DHMM_GCHUNK, C - c0);
+        const int64_t tiles = group_start ? P / 64 + nc : nc * ((N + 63) / 64);
+        const int G = DIR ? std::min(pl.G, dhmm_waves(tiles, T, true)) : dhmm_waves(tiles, T, false);
+        const double *rc = rec + (size_t)c0 * R;
+        const int32_t *gs = group_start ? group_start + c0 : nullptr;
+        hipError_t e;
+        if (NS == 8)
+            e = dhmm_launch<8, DIR>(dim3((unsigned)G), lds, s, rc, n_states + c0, (int)c0, (int)nc, C, Smax, K, sym, len, N, T,
+                                    gs, members, (int)P, score, seg, dir);
+        else if (NS == 16)
+            e = dhmm_launch<16, DIR>(dim3((unsigned)G), lds, s, rc, n_states + c0, (int)c0, (int)nc, C, Smax, K, sym, len, N, T,
+                                     gs, members, (int)P, score, seg, dir);
+        else
+            e = dhmm_launch<32, DIR>(dim3((unsigned)G), lds, s, rc, n_states + c0, (int)c0, (int)nc, C, Smax, K, sym, len, N, T,
+                                     gs, members, (int)P, score, seg, dir);
+        if (e != hipSuccess) return DSP_ERR_HIP + (int)e;
+    }
+    return dtw_launch_status();
+}
+
+}  // namespace dsp
+
+extern "C" size_t dsp_dhmm_workspace_bytes(int64_t C, int64_t N, int64_t P, int T, int Smax, int K)
+{
+    if (!dsp::dhmm_in_plan(C, N, P, T, Smax, K)) return 0;
+    return dsp::dhmm_plan(C, N, P, T, Smax, K).total();
+}
+
+extern "C" int dsp_dhmm_score(const double *emit, const double *stay, const double *adv, const int32_t *n_states, int64_t C,
+                              int Smax, int K, const int32_t *sym, const int32_t *len, int64_t N, int T, double *score,
+                              int32_t *label, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!dsp::dhmm_in_plan(C, N, 0, T, Smax, K)) return DSP_ERR_ARGS;
+    if (N == 0 || (!score && !label)) return DSP_OK;
+    if (!sym || !len || (C > 0 && (!emit || !stay || !adv || !n_states))) return DSP_ERR_ARGS;
+    const dsp::DhmmPlan pl = dsp::dhmm_plan(C, N, 0, T, Smax, K);
+    if (!workspace || workspace_bytes < pl.total()) return DSP_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    double *sc = score ? score : (double *)((char *)workspace + pl.rec + pl.dir);
+    if (C > 0) {
+        const int rc = dsp::dhmm_run<false>(s, pl, workspace, emit, stay, adv, n_states, C, Smax, K, sym, len, N, T, nullptr,
+                                            nullptr, 0, sc, nullptr);
+        if (rc != DSP_OK) return rc;
+    }
+    if (label) hipLaunchKernelGGL(dsp::csr_label, dsp::csr_grid(N), dim3(256), 0, s, sc, N, C, label);
+    return dsp::dtw_launch_status();
+}
+
+extern "C" int dsp_dhmm_align(const double *emit, const double *stay, const double *adv, const int32_t *n_states, int64_t C,
+                              int Smax, int K, const int32_t *sym, const int32_t *len, int64_t N, int T,
+                              const int32_t *group_start, const int32_t *members, int64_t P, double *score, int32_t *seg,
+                              void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!dsp::dhmm_in_plan(C, N, P, T, Smax, K)) return DSP_ERR_ARGS;
+    if (C == 0 || P == 0 || (!score && !seg)) return DSP_OK;
+    if (!emit || !stay || !adv || !n_states || !group_start || !members || (N > 0 && (!sym || !len))) return DSP_ERR_ARGS;
+    const dsp::DhmmPlan pl = dsp::dhmm_plan(C, N, P, T, Smax, K);
+    if (!workspace || workspace_bytes < pl.total()) return DSP_ERR_WORKSPACE;
+    if (seg)
+        return dsp::dhmm_run<true>((hipStream_t)stream, pl, workspace, emit, stay, adv, n_states, C, Smax, K, sym, len, N, T,
+                                   group_start, members, P, score, seg);
+    return dsp::dhmm_run<false>((hipStream_t)stream, pl, workspace, emit, stay, adv, n_states, C, Smax, K, sym, len, N, T,
+                                group_start, members, P, score, nullptr);
+}
+
+extern "C" int dsp_dhmm_accumulate(const int32_t *n_states, int64_t C, int Smax, int K, const int32_t *sym,
+                                   const int32_t *len, int64_t N, int T, const int32_t *group_start, const int32_t *members,
+                                   int64_t P, const int32_t *seg, const double *score, int32_t *cnt_emit, int32_t *cnt,
+                                   int32_t *n_valid, double *total, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!dsp::dhmm_in_plan(C, N, P, T, Smax, K)) return DSP_ERR_ARGS;
+    if (C == 0) return DSP_OK;
+    if (!n_states || !group_start || !cnt_emit || !cnt || !n_valid || !total || (P > 0 && (!members || !seg || !score)) ||
+        (N > 0 && (!sym || !len)))
+        return DSP_ERR_ARGS;
+    const dsp::DhmmPlan pl = dsp::dhmm_plan(C, N, P, T, Smax, K);
+    if (!workspace || workspace_bytes < pl.total()) return DSP_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    int32_t *pmodel = (int32_t *)((char *)workspace + pl.rec + pl.dir + pl.score);
+    const dim3 block(256);
+    hipLaunchKernelGGL(dsp::csr_zero_counts, dsp::csr_grid(C * Smax * (int64_t)(K + 1)), block, 0, s, cnt_emit,
+                       C * Smax * (int64_t)K, cnt, C * (int64_t)Smax);
+    if (P > 0) {
+        hipLaunchKernelGGL(dsp::dhmm_pairs, dsp::csr_grid(P), block, 0, s, n_states, C, Smax, K, sym, len, N, T, group_start,
+                           members, P, seg, pmodel);
+        hipLaunchKernelGGL(dsp::dhmm_count, dsp::csr_grid(P * T), block, 0, s, n_states, Smax, K, sym, len, T, members, P, seg,
+                           pmodel, cnt_emit, cnt);
+    }
+    hipLaunchKernelGGL(dsp::dhmm_totals, dsp::csr_grid(C), block, 0, s, C, group_start, P, pmodel, score, n_valid, total);
+    return dsp::dtw_launch_status();
+}

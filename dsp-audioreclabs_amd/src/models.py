@@ -540,6 +540,106 @@ class VqClassifier(SequenceClassifier):
         return self.classes_[label.cpu().numpy()]
 
 
+class DiscreteHmmClassifier(SequenceClassifier):
+    """One left-to-right HMM with discrete observations per class over ONE shared vector-quantisation
+    codebook: the frames are quantised once (``pipeline.VqTokenizer``), every state emits symbols with a
+    probability table, and the models are trained by Viterbi re-estimation -- integer counts, so the
+    statistics need no summation order.  csrc/dhmm.hip (dsp_dhmm_score, dsp_dhmm_align,
+    dsp_dhmm_accumulate).  Input handling and normalisation are ``SequenceClassifier``'s.
+
+    n_states     states per model: an int, or one value per class (sorted class values), each in 1 .. 32.
+    n_codes      codewords of the shared codebook, the alphabet: a power of two in 1 .. 256.
+    n_iter       rounds of align -> accumulate -> rebuild after the uniform start; training stops early
+                 when a round changes no segment boundary.
+    alpha        the additive smoothing of the emission tables (> 0), see ``pipeline.DhmmModelSet``.
+    trans_floor  p_stay is clamped to [trans_floor, 1 - trans_floor].
+    vq_iter, eps the tokeniser's Lloyd rounds per level and its split offset (``VqClassifier``'s n_iter, eps).
+    ``fit``: the training set, the tokeniser's fit and transform on the scaled training set, the uniform
+    segmentation, one accumulate, then the rounds.  A training sequence shorter than its class's n_states
+    is left out of that class's statistics; a class none of whose members is long enough raises ValueError.
+    ``predict`` raises ValueError for a query with fewer frames than every model has states
+    (``score_samples`` returns its row of +inf).
+    After ``fit``: tokenizer_ (``pipeline.VqTokenizer``), model_ (``pipeline.DhmmModelSet``: emit, stay, adv,
+    n_states), totals_ float64 [rounds run, C], n_iter_ the rounds run.
+    No CPU path: ``fit`` and ``predict`` raise HipError without a HIP device (constructing needs none).
+    """
+
+    def __init__(self, n_states=5, n_codes=64, n_iter=10, alpha=0.5, trans_floor=1e-3, vq_iter=10, eps=0.01,
+                 normalize=True):
+        super().__init__(n_neighbors=1, window=None, normalize=normalize)
+        from .pipeline import HMM_MAX_STATES, VqTokenizer
+        states = np.asarray(n_states)
+        if states.ndim > 1 or states.size < 1 or not np.issubdtype(states.dtype, np.integer):
+            raise ValueError("n_states must be an int or one int per class")
+        if states.min() < 1 or states.max() > HMM_MAX_STATES:
+            raise ValueError("n_states must lie in [1, %d]" % HMM_MAX_STATES)
+        self.n_states = int(states) if states.ndim == 0 else states.astype(np.int32)
+        VqTokenizer(n_codes, vq_iter, eps)  # its argument checks
+        self.n_codes, self.vq_iter, self.eps = int(n_codes), int(vq_iter), float(eps)
+        self.n_iter, self.alpha, self.trans_floor = int(n_iter), float(alpha), float(trans_floor)
+        if self.n_iter < 0 or not self.alpha > 0.0 or not np.isfinite(self.alpha):
+            raise ValueError("n_iter must be >= 0 and alpha a positive number")
+        if not 0.0 < self.trans_floor < 0.5:
+            raise ValueError("trans_floor must lie in (0, 0.5)")
+
+    def fit(self, X, y, lengths=None):
+        from .pipeline import DhmmModelSet, DhmmUpdater, VqTokenizer, hmm_uniform_segmentation
+        X, n, codes = self._training_set(X, y, lengths)
+        C, K = len(self.classes_), self.n_codes
+        states = np.full(C, self.n_states, np.int32) if np.ndim(self.n_states) == 0 else self.n_states
+        if len(states) != C:
+            raise ValueError("%d n_states for %d classes" % (len(states), C))
+        Smax = int(states.max())
+        order = np.argsort(codes, kind="stable")  # each class's members in training order
+        start = np.concatenate([[0], np.cumsum(np.bincount(codes, minlength=C))])
+        longest = np.array([n[order[start[c]:start[c + 1]]].max() for c in range(C)])
+        if (longest < states).any():
+            c = int(np.argmax(longest < states))
+            raise ValueError("class %r has no sequence of at least n_states = %d frames" % (self.classes_[c], states[c]))
+        self.tokenizer_ = VqTokenizer(K, self.vq_iter, self.eps).fit(X, n)
+        updater = DhmmUpdater(self.tokenizer_.transform(X, n), n, start, order)
+        seg = hmm_uniform_segmentation(n[order], states[codes[order]], Smax)
+        stats = updater.accumulate(states, K, seg, np.zeros(len(order)))
+        model = DhmmModelSet(*stats[:3], states, self.alpha, self.trans_floor)
+        totals = []
+        for _ in range(self.n_iter):
+            score, new_seg = updater.align(model)
+            stats = updater.accumulate(states, K, new_seg, score)
+            totals.append(stats[3].cpu().numpy())
+            model = DhmmModelSet(*stats[:3], states, self.alpha, self.trans_floor, prev=model)
+            new_seg = new_seg.cpu().numpy()
+            same = np.array_equal(new_seg, seg)
+            seg = new_seg
+            if same:
+                break
+        self.model_, self.n_iter_ = model, len(totals)
+        self.totals_ = np.array(totals, dtype=np.float64).reshape(len(totals), C)
+        return self
+
+    def _scores(self, X, lengths, with_labels):
+        from .pipeline import dhmm_score
+        Xq, nq = _as_padded(X, lengths)
+        if Xq.shape[2] != self.tokenizer_.codebook_.shape[1]:
+            raise ValueError("X has %d feature channels, the fitted codebook %d"
+                             % (Xq.shape[2], self.tokenizer_.codebook_.shape[1]))
+        sym = self.tokenizer_.transform(self._scale(Xq, nq), nq)
+        return dhmm_score(self.model_, sym, nq, with_labels=with_labels)
+
+    def score_samples(self, X, lengths=None):
+        """float64 [n, C]: each sequence's negative log-likelihood along its best state path under each
+        class's model (+inf where the sequence has fewer frames than the model has states)."""
+        return self._scores(X, lengths, False)[0].cpu().numpy()
+
+    def kneighbors(self, X, lengths=None):
+        raise NotImplementedError("an HMM classifier keeps no training sequences")
+
+    def predict(self, X, lengths=None):
+        label = self._scores(X, lengths, True)[1].cpu().numpy()
+        if (label < 0).any():
+            raise ValueError("sequence %d has fewer frames than every model has states" % int(np.argmax(label < 0)))
+        return self.classes_[label]
+
+
 # ==================== MLP (models.py:77-221) ====================
 
 def _build_network(input_size, hidden_layers, num_classes, dropout):
@@ -806,8 +906,8 @@ def fit_mlp_models(X_train, y_train, input_size, hidden_layers, num_classes, lea
 
 
 def create_classifier(classifier_type, **kwargs):
-    """models.py:226-246.  'mlp' takes MLPTrainer's arguments; 'dtw_knn', 'dtw_template', 'hmm' and 'vq' (extensions) are
-    the SequenceClassifier, the TemplateClassifier, the HmmClassifier and the VqClassifier.  A bare ``create_classifier('mlp')``
+    """models.py:226-246.  'mlp' takes MLPTrainer's arguments; 'dtw_knn', 'dtw_template', 'hmm', 'vq' and 'dhmm' (extensions) are
+    the SequenceClassifier, the TemplateClassifier, the HmmClassifier, the VqClassifier and the DiscreteHmmClassifier.  A bare ``create_classifier('mlp')``
     raises NotImplementedError naming them (the reference fails there with a TypeError)."""
     if classifier_type in ['knn', 'naive_bayes', 'decision_tree', 'svm']:
         return TraditionalClassifier(classifier_type, **kwargs)
@@ -819,6 +919,8 @@ def create_classifier(classifier_type, **kwargs):
         return HmmClassifier(**kwargs)
     if classifier_type == 'vq':
         return VqClassifier(**kwargs)
+    if classifier_type == 'dhmm':
+        return DiscreteHmmClassifier(**kwargs)
     if classifier_type == 'mlp':
         if not kwargs:
             raise NotImplementedError("create_classifier('mlp') needs input_size, hidden_layers and num_classes "

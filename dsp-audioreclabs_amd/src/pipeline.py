@@ -796,6 +796,236 @@ def vq_repair_empty(cb, cnt, n_codes, eps):
     return cb, cnt
 
 
+DHMM_MAX_SYMBOLS = 256  # symbols of the shared alphabet at most (csrc/dhmm.hip stages a model's table into LDS)
+
+
+class DhmmModelSet:
+    """C left-to-right HMMs with discrete observations padded to Smax states over an alphabet of K
+    symbols, in the form ``dsp_dhmm_score`` reads (include/dsp_audiorec.h): emit float64 [C, Smax, K],
+    stay, adv float64 [C, Smax] and n_states int32 [C], numpy arrays on the host, built from the counts
+    of ``dsp_dhmm_accumulate``.  This is the only place a logarithm is taken:
+        emit = -log((cnt_emit + alpha) / (cnt + alpha * K))    in exactly that order, alpha * K one rounded product
+        p_stay = (cnt - n_valid) / cnt, clamped to [trans_floor, 1 - trans_floor]
+        stay = -log(p_stay);  adv = -log(1 - p_stay)
+    ``alpha`` > 0, so a state nothing was counted for comes out uniform by itself.  Rows s >= n_states[c]
+    are zeros.  A model with n_valid == 0 keeps ``prev``'s stay / adv (p_stay = 0.5 without ``prev``); its
+    emissions come from its (all-zero) counts like any other's.  ``from_arrays`` takes a hand-built set."""
+
+    def __init__(self, cnt_emit, cnt, n_valid, n_states, alpha=0.5, trans_floor=1e-3, prev=None):
+        cnt_emit, cnt, n_valid, n_states = (_as_host(v).astype(np.int64) for v in (cnt_emit, cnt, n_valid, n_states))
+        if cnt_emit.ndim != 3 or cnt.shape != cnt_emit.shape[:2]:
+            raise ValueError("cnt_emit must be [C, Smax, K] and cnt [C, Smax]")
+        C, Smax, K = cnt_emit.shape
+        self._check(C, Smax, K, n_states)
+        if n_valid.shape != (C,):
+            raise ValueError("n_valid must be [C]")
+        if not (alpha > 0.0 and np.isfinite(alpha)):
+            raise ValueError("alpha must be a positive number")
+        if not 0.0 < trans_floor < 0.5:
+            raise ValueError("trans_floor must lie in (0, 0.5)")
+        alpha = np.float64(alpha)
+        valid = np.arange(Smax)[None, :] < n_states[:, None]
+        den = cnt.astype(np.float64) + alpha * np.float64(K)
+        emit = -np.log((cnt_emit.astype(np.float64) + alpha) / den[:, :, None])
+        seen = valid & (cnt > 0) & (n_valid[:, None] > 0)
+        cf = np.where(seen, cnt, 2).astype(np.float64)
+        p = (cf - np.where(seen, n_valid[:, None], 1).astype(np.float64)) / cf
+        p = np.minimum(np.maximum(p, trans_floor), 1.0 - trans_floor)
+        stay, adv = -np.log(p), -np.log(1.0 - p)
+        if prev is not None:
+            keep = (n_valid == 0)[:, None]
+            stay, adv = np.where(keep, prev.stay, stay), np.where(keep, prev.adv, adv)
+        self.n_states = n_states.astype(np.int32)
+        self.emit = np.where(valid[:, :, None], emit, 0.0)
+        self.stay, self.adv = np.where(valid, stay, 0.0), np.where(valid, adv, 0.0)
+        self._dev = None
+
+    @staticmethod
+    def _check(C, Smax, K, n_states):
+        if n_states.shape != (C,) or not 1 <= Smax <= HMM_MAX_STATES or not 1 <= K <= DHMM_MAX_SYMBOLS:
+            raise ValueError("n_states must be [C], 1 <= Smax <= %d, 1 <= K <= %d" % (HMM_MAX_STATES, DHMM_MAX_SYMBOLS))
+        if C and (n_states.min() < 1 or n_states.max() > Smax):
+            raise ValueError("n_states must lie in [1, %d]" % Smax)
+
+    @classmethod
+    def from_arrays(cls, emit, stay, adv, n_states):
+        """A hand-built set: emit [C, Smax, K], stay, adv [C, Smax] as they are (finite or +inf, never NaN,
+        never -inf), n_states [C]."""
+        emit, stay, adv = (np.array(_as_host(v, np.float64)) for v in (emit, stay, adv))
+        n_states = _as_host(n_states).astype(np.int64).reshape(-1)
+        if emit.ndim != 3 or stay.shape != emit.shape[:2] or adv.shape != emit.shape[:2]:
+            raise ValueError("emit must be [C, Smax, K] and stay, adv [C, Smax]")
+        cls._check(*emit.shape, n_states)
+        for v in (emit, stay, adv):
+            if np.isnan(v).any() or (v == -np.inf).any():
+                raise ValueError("costs must be finite or +inf")
+        self = cls.__new__(cls)
+        self.emit, self.stay, self.adv, self.n_states, self._dev = emit, stay, adv, n_states.astype(np.int32), None
+        return self
+
+    @property
+    def shape(self):
+        return self.emit.shape
+
+    def on_device(self, device):
+        """(emit, stay, adv, n_states) as device tensors, uploaded once."""
+        import torch
+        if self._dev is None or self._dev[0].device != torch.device(device):
+            self._dev = tuple(_as_device(a, torch.float64, device) for a in (self.emit, self.stay, self.adv))
+            self._dev += (_as_device(self.n_states, torch.int32, device),)
+        return self._dev
+
+
+_DHMM_SHAPE = ("unsupported discrete HMM shape (1 <= T <= 1024, 1 <= Smax <= %d, 1 <= K <= %d)"
+               % (HMM_MAX_STATES, DHMM_MAX_SYMBOLS))
+
+
+def _dhmm_operand(sym, lengths, device):
+    """Symbol rows [N, T] and their lengths on the device as int32."""
+    import torch
+    s = _as_device(sym, torch.int32, device)
+    if s.dim() != 2:
+        raise ValueError("symbols must be padded to [N, T], got shape %s" % (tuple(s.shape),))
+    n = _as_device(lengths, torch.int32, device).reshape(-1)
+    if n.numel() != s.shape[0]:
+        raise ValueError("%d lengths for %d symbol rows" % (n.numel(), s.shape[0]))
+    return s.contiguous(), n
+
+
+def _dhmm_model_args(models, device):
+    C, Smax, K = models.shape
+    return [_hip.ptr(t) for t in models.on_device(device)] + [C, Smax, K]
+
+
+def dhmm_score(models, sym, lengths, with_labels=False, _ws=None):
+    """Viterbi scores (include/dsp_audiorec.h: dsp_dhmm_score) of the symbol rows sym int32 [N, T] under
+    every model of the ``DhmmModelSet``: (score float64 [N, C], +inf where the sequence is shorter than
+    the model or holds a symbol outside the alphabet; label int32 [N] or None: the smallest score's model,
+    -1 when every score is +inf) on the device."""
+    import torch
+    d = _hip.require_device()
+    s, n = _dhmm_operand(sym, lengths, d)
+    N, T = s.shape
+    margs = _dhmm_model_args(models, d)
+    C, Smax, K = margs[-3:]
+    score = torch.empty((N, C), dtype=torch.float64, device=d)
+    label = torch.empty(N, dtype=torch.int32, device=d) if with_labels else None
+    if N > 0:
+        ws = _grown(_ws, _hip.lib().dsp_dhmm_workspace_bytes(C, N, 0, T, Smax, K), _DHMM_SHAPE, d)
+        rc = _hip.lib().dsp_dhmm_score(*margs, _hip.ptr(s), _hip.ptr(n), N, T, _hip.ptr(score), _hip.ptr(label),
+                                       _hip.ptr(ws), ws.numel(), _hip.stream_handle(d))
+        _hip.check(rc, "dsp_dhmm_score")
+    return score, label
+
+
+class DhmmUpdater(_PairListPlan):
+    """The symbol rows of a Viterbi training run uploaded once with their CSR class lists (one group per
+    model): the plan's ``seqs`` is the int32 [N, T] tensor; the workspace is held across iterations.
+    ``align`` is one ``dsp_dhmm_align`` call for all models, ``accumulate`` one ``dsp_dhmm_accumulate`` call."""
+
+    def __init__(self, sym, lengths, group_start, members):
+        import torch
+        self.device = d = _hip.require_device()
+        self.seqs, self.len_s = _dhmm_operand(sym, lengths, d)
+        self.N, self.T = self.seqs.shape
+        self.C = len(group_start) - 1
+        start, members = _dtw_groups((group_start, members), None, self.C, self.N)
+        self.P = int(members.size)
+        self.start, self.members = _as_device(start, torch.int32, d), _as_device(members, torch.int32, d)
+        self._ws = None
+
+    def _workspace(self, Smax, K):
+        return self._grow(_hip.lib().dsp_dhmm_workspace_bytes(self.C, self.N, self.P, self.T, Smax, K), _DHMM_SHAPE)
+
+    def align(self, models, with_seg=True):
+        """(score float64 [P], seg int32 [P, Smax] or None) of every listed pair."""
+        import torch
+        d = self.device
+        margs = _dhmm_model_args(models, d)
+        C, Smax, K = margs[-3:]
+        if C != self.C:
+            raise ValueError("%d models for %d groups" % (C, self.C))
+        score = torch.empty(self.P, dtype=torch.float64, device=d)
+        seg = torch.empty((self.P, Smax), dtype=torch.int32, device=d) if with_seg else None
+        if self.P > 0 and C > 0:
+            ws = self._workspace(Smax, K)
+            rc = _hip.lib().dsp_dhmm_align(*margs, _hip.ptr(self.seqs), _hip.ptr(self.len_s), self.N, self.T,
+                                           _hip.ptr(self.start), _hip.ptr(self.members), self.P, _hip.ptr(score),
+                                           _hip.ptr(seg), _hip.ptr(ws), ws.numel(), _hip.stream_handle(d))
+            _hip.check(rc, "dsp_dhmm_align")
+        return score, seg
+
+    def accumulate(self, n_states, K, seg, score):
+        """The re-estimation from a given segmentation: (cnt_emit int32 [C, Smax, K], cnt int32 [C, Smax],
+        n_valid int32 [C], total float64 [C]) on the device."""
+        import torch
+        d = self.device
+        n_states, seg = _as_device(n_states, torch.int32, d).reshape(-1), _as_device(seg, torch.int32, d)
+        score = _as_device(score, torch.float64, d).reshape(-1)
+        C, K = self.C, int(K)
+        if seg.dim() != 2 or n_states.numel() != C or seg.shape[0] != self.P or score.numel() != self.P:
+            raise ValueError("%d n_states, seg %s for %d groups, %d pairs" % (n_states.numel(), tuple(seg.shape), C, self.P))
+        Smax = seg.shape[1]
+        cnt_emit = torch.empty((C, Smax, K), dtype=torch.int32, device=d)
+        cnt = torch.empty((C, Smax), dtype=torch.int32, device=d)
+        n_valid = torch.empty(C, dtype=torch.int32, device=d)
+        total = torch.empty(C, dtype=torch.float64, device=d)
+        if C > 0:
+            ws = self._workspace(Smax, K)
+            rc = _hip.lib().dsp_dhmm_accumulate(_hip.ptr(n_states), C, Smax, K, _hip.ptr(self.seqs), _hip.ptr(self.len_s),
+                                                self.N, self.T, _hip.ptr(self.start), _hip.ptr(self.members), self.P,
+                                                _hip.ptr(seg.contiguous()), _hip.ptr(score), _hip.ptr(cnt_emit), _hip.ptr(cnt),
+                                                _hip.ptr(n_valid), _hip.ptr(total), _hip.ptr(ws), ws.numel(),
+                                                _hip.stream_handle(d))
+            _hip.check(rc, "dsp_dhmm_accumulate")
+        return cnt_emit, cnt, n_valid, total
+
+
+def dhmm_align(models, sym, lengths, groups=None, assign=None, with_seg=True):
+    """Viterbi state paths (include/dsp_audiorec.h: dsp_dhmm_align) of the symbol rows sym[members[p]]
+    under model c, the pairs given as the CSR ``groups=(group_start [C + 1], members [P])`` or as ``assign``
+    [N] (the model of each sequence, -1 to skip).  Returns (score float64 [P], seg int32 [P, Smax] or None,
+    group_start, members) on the device, seg as ``hmm_align``'s."""
+    N = len(lengths)
+    start, members = _dtw_groups(groups, assign, models.shape[0], N)
+    up = DhmmUpdater(sym, lengths, start, members)
+    score, seg = up.align(models, with_seg)
+    return score, seg, up.start, up.members
+
+
+class VqTokenizer:
+    """ONE vector-quantisation codebook shared by all sequences: the tokeniser in front of the discrete
+    HMMs.  ``fit`` trains it by LBG binary splitting on all sequences together -- by definition the
+    codebook ``models.VqClassifier(n_codes, n_iter, eps, normalize=False)`` gives for all-equal labels, bit
+    for bit; ``transform`` is one ``dsp_vq_assign`` with members = 0 .. N-1.
+    After ``fit``: codebook_ float64 [n_codes, F]."""
+
+    def __init__(self, n_codes, n_iter=10, eps=0.01):
+        from .models import VqClassifier
+        VqClassifier(n_codes, n_iter, eps, normalize=False)  # its argument checks
+        self.n_codes, self.n_iter, self.eps = int(n_codes), int(n_iter), float(eps)
+        self._dev = None
+
+    def fit(self, X, lengths):
+        from .models import VqClassifier
+        lengths = _as_host(lengths).astype(np.int32).reshape(-1)
+        clf = VqClassifier(self.n_codes, self.n_iter, self.eps, normalize=False)
+        self.codebook_ = clf.fit(_as_host(X, np.float64), np.zeros(len(lengths), np.int32), lengths).codebooks_[0]
+        self._dev = None
+        return self
+
+    def transform(self, X, lengths):
+        """sym int32 [N, T] on the device: each frame's nearest codeword (-1 behind a sequence's frames)."""
+        import torch
+        d = _hip.require_device()
+        if self._dev is None or self._dev.device != torch.device(d):
+            self._dev = _as_device(self.codebook_[None], torch.float64, d)
+        N = len(lengths)
+        _, code, _, _ = vq_assign(self._dev, np.array([self.n_codes], np.int32), X, lengths,
+                                  groups=([0, N], np.arange(N)), check_finite=False)
+        return code
+
+
 class _CropFramePlan:
     """What the launch plans of the two crop-frame kernels (csrc/crop_frames.h) share: ``PitchTracker`` and
     ``LpcAnalyzer`` run after a ``FeatureExtractor`` call, on that call's device outputs, and validate

@@ -36,7 +36,7 @@ extern "C" {
                               5: queue_ws is 4 KiB (each counter on its own 256-B line);
                               6: the extraction entry points take out_stride (packed result rows);
                                  dsp_knn_classify takes flags (DSP_KNN_REF_READY).
-                              Still 6 with the dsp_mlp_*, dsp_svc_*, dsp_gnb_*, dsp_tree_* and dsp_dtw_* (dsp_dtw_align, dsp_dtw_dba_update included) and dsp_hmm_* and dsp_vq_* and dsp_pitch_* and dsp_lpc_* entry points: new symbols only, no
+                              Still 6 with the dsp_mlp_*, dsp_svc_*, dsp_gnb_*, dsp_tree_* and dsp_dtw_* (dsp_dtw_align, dsp_dtw_dba_update included) and dsp_hmm_* and dsp_vq_* and dsp_dhmm_* and dsp_pitch_* and dsp_lpc_* entry points: new symbols only, no
                               existing signature or meaning changed, so callers built against 6 keep
                               working (a binding that needs them checks for the symbols) */
 
@@ -650,6 +650,68 @@ int dsp_vq_accumulate(const double *cb_prev, const int32_t *n_codes, int64_t C, 
                       const int32_t *members, int64_t P, const int32_t *code, const double *dist,
                       double *centroid, int32_t *cnt, int32_t *n_valid, double *total, void *workspace,
                       size_t workspace_bytes, void *stream);
+
+/*
+ * Left-to-right hidden Markov models with DISCRETE observations: the frames are quantised once against
+ * one shared codebook (dsp_vq_assign with members = 0 .. N-1 of one group is the tokeniser) and every
+ * state emits symbols with a probability table.  csrc/dhmm.hip, DESIGN.md §4.14.  An extension like the
+ * entry points above from dsp_dtw_* on: nothing here restates a reference file.  Every output is defined
+ * bit for bit: the device computes fp64 add and min in the order below, each operation rounded, and
+ * integer counts; the logarithms are the caller's, taken when the model is built.
+ *
+ * Symbols: sym int32 [N, T] padded row-major with len int32 [N], 1 <= T <= 1024 -- the layout of
+ *   dsp_vq_assign's code.  Entries at t >= len are never read through, whatever they hold.
+ * Alphabet: K symbols, 1 <= K <= 256, shared by all models of a set.
+ * Model set: C <= 2^20 models padded to Smax states, 1 <= n_states[c] <= Smax <= 32: emit float64
+ *   [C, Smax, K] (= -log b_s(k)), stay, adv float64 [C, Smax], n_states int32 [C].  All finite or +inf,
+ *   never NaN, never -inf; adv[c, S-1] and the rows s >= S are never read.
+ * Recurrence, for a sequence of length n and a model of S states:
+ *     e(t,s) = emit[c, s, sym[t]]
+ *     V(0,0) = e(0,0);  V(0,s>0) = +inf
+ *     a = V(t-1,s) + stay[s];  b = V(t-1,s-1) + adv[s-1]        (b = +inf at s = 0)
+ *     V(t,s) = e(t,s) + min(a, b)
+ *     score  = V(n-1, S-1)
+ *   score is +inf when n < S, when n < 1 or n > T, when n_states[c] is outside 1 .. Smax, for a list
+ *   entry outside [0, N), and when any sym[t], t < n, lies outside [0, K) (such a symbol never indexes
+ *   the table).
+ * Path, seg int32 [P, Smax] and the -1 rules: dsp_hmm_align's above, word for word (advance iff b < a).
+ * Pairs (dsp_dhmm_align, dsp_dhmm_accumulate): dsp_dtw_align's CSR list over the models.
+ *
+ * dsp_dhmm_score: every sequence against every model, score float64 [N, C]; label int32 [N] the model of
+ *   the smallest score, ties to the smaller index, -1 when every score is +inf.  Either may be NULL.
+ * dsp_dhmm_align: score float64 [P] and seg int32 [P, Smax] of the listed pairs; either may be NULL
+ *   (without seg no direction bit is stored and no path is walked).
+ * dsp_dhmm_accumulate: the Viterbi re-estimate from a GIVEN seg [P, Smax] and score [P].  A member is
+ *   valid when its index and length are, its seg row is well formed for its model (seg[0] = 0, strictly
+ *   increasing over the S states, seg[S-1] < n) and every sym[t], t < n, lies in [0, K); any other member
+ *   is skipped whole.  Outputs:
+ *     cnt_emit int32 [C, Smax, K]  frames of valid members that sit in state s and carry symbol k
+ *     cnt      int32 [C, Smax]     frames of valid members in state s
+ *     n_valid  int32 [C]           valid members
+ *     total    float64 [C]         their scores added in list order, the first being the value itself
+ *   Rows s >= S are zeros.  A model with no valid member or an n_states outside 1 .. Smax has all-zero
+ *   counts, total 0.0 and n_valid 0.
+ * workspace  device scratch of dsp_dhmm_workspace_bytes(C, N, P, T, Smax, K) bytes (0: sizes outside the
+ *   plan; P = 0 for dsp_dhmm_score): the model set repacked (emission tables transposed to one row per
+ *   symbol), one 32-bit direction word per row and lane for each resident wave (at most 256 MiB), N x C
+ *   scores (labels without scores), and one int32 per pair for the re-estimation.  Nothing in it is
+ *   carried from one call to the next.
+ * All three check their host arguments before any launch (DSP_ERR_ARGS, DSP_ERR_WORKSPACE), return
+ * DSP_OK with nothing to do, make no host synchronisation and no allocation, and write only to their
+ * outputs and the workspace, on the caller's stream.
+ */
+size_t dsp_dhmm_workspace_bytes(int64_t C, int64_t N, int64_t P, int T, int Smax, int K);
+int dsp_dhmm_score(const double *emit, const double *stay, const double *adv, const int32_t *n_states, int64_t C,
+                   int Smax, int K, const int32_t *sym, const int32_t *len, int64_t N, int T, double *score,
+                   int32_t *label, void *workspace, size_t workspace_bytes, void *stream);
+int dsp_dhmm_align(const double *emit, const double *stay, const double *adv, const int32_t *n_states, int64_t C,
+                   int Smax, int K, const int32_t *sym, const int32_t *len, int64_t N, int T,
+                   const int32_t *group_start, const int32_t *members, int64_t P, double *score, int32_t *seg,
+                   void *workspace, size_t workspace_bytes, void *stream);
+int dsp_dhmm_accumulate(const int32_t *n_states, int64_t C, int Smax, int K, const int32_t *sym, const int32_t *len,
+                        int64_t N, int T, const int32_t *group_start, const int32_t *members, int64_t P,
+                        const int32_t *seg, const double *score, int32_t *cnt_emit, int32_t *cnt, int32_t *n_valid,
+                        double *total, void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * Short-time autocorrelation pitch track -- the fourth classical time-domain feature next to energy,
