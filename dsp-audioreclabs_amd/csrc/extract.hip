@@ -5,7 +5,7 @@
 // registers (each thread holds EXTRACT_RREG 32-sample words):
 //   R1  registers: integer sum / min / max + exact per-word moments (sum k, sum k^2) -> LDS
 //   R2  registers: positive-sample bits per word -> LDS (the ZCR of any range is a popcount)
-//   R3  endpoint detection from the per-word summaries (+ the two partial words of each frame;
+//   R3  endpoint detection from the per-word summaries (+ the half-word at each end of a frame;
 //       sign changes from per-segment prefixes), p90 by one wave's repeated maxima, double-
 //       threshold scan
 //   R4  windowed frames of the crop (clip-relative vectors re-read from L2, window from LDS)
@@ -409,9 +409,10 @@ __device__ __forceinline__ int vad_scan(const ExtractParams &p, const Ctx &c, in
     return flag;
 }
 
-// Endpoint frame ends (pass A): boundary t = 2f (start) / 2f + 1 (end) of VAD frame f lies inside
-// a buffer word that the frame only partly covers; returns that word (or -1: the boundary is
-// word aligned, or t >= 2 nv) and the covered element range [e0, e1) of it.
+// Endpoint frame ends (pass A) of the runtime layout (clip_body): boundary t = 2f (start) / 2f + 1
+// (end) of VAD frame f lies inside a buffer word that the frame only partly covers; returns that
+// word (or -1: the boundary is word aligned, or t >= 2 nv) and the covered element range [e0, e1)
+// of it.  (clip_fast sums half a word per boundary instead: frame_end_pos, below)
 __device__ __forceinline__ int vad_partial_word(const ClipRef &cur, int L, int S, int nv, int t, int &e0, int &e1)
 {
     e0 = e1 = 0;
@@ -432,29 +433,47 @@ __device__ __forceinline__ int vad_partial_word(const ClipRef &cur, int L, int S
     }
     return -1;
 }
-// FAST pass A: partial_moments unrolled over the word's four vectors (no value selects) and with the
-// squares of two pairs chained in one 32-bit v_dot2 (as R1's interior words: 4 x 32768^2 = 2^32
-// wraps only when all four samples are -32768, so a clip holding a -32768 sample (kneg, clip-
-// uniform) adds every pair's squares to the 64-bit sum on its own)
-__device__ __forceinline__ void partial_moments_fast(const short8 (&q)[4], int e0, int e1, bool kneg, int &t1,
-                                                     unsigned long long &t2)
+// FAST pass A sums half a word per frame end.  Frame f = buffer samples [u0, u1), u0 = lead + f S,
+// u1 = u0 + L, and T(w) = the exact moments of word w's real samples (wS1 / wS2, edge words
+// included):   sum over the frame = sum of T over words u0 >> 5 .. (u1 - 1) >> 5 inclusive
+//                                   - Lo (the first word's elements below the start)
+//                                   - H  (the last word's elements from the end on),
+// for any frame, one inside a single word included.  Boundary t = 2f + h (h = 0 start, 1 end) sits
+// at element e of word w: a start at (u0 >> 5, u0 & 31), e = 0 .. 31; an end at the last word and
+// e = u1 - 32 w = 1 .. 32.  frame_end_pos returns x = u0 + h (L - 1): w = x >> 5, e = (x & 31) + h.
+// The boundary lies in one 16-sample half of its word: for e <= 16 the masked sum P over the low
+// half is Lo, for e > 16 P over the high half is H, and the other one is T(w) - P (exact integers).
+// An aligned boundary (start e = 0, end e = 32) keeps no element: P = 0 is the quantity wanted.
+__device__ __forceinline__ int frame_end_pos(int lead, int L, int S, int t)
 {
-    const uint32_t hi = e1 >= 32 ? ~0u : (1u << e1) - 1u;
-    const uint32_t M = hi & ~((1u << e0) - 1u);  // e0 < 32
-    const short2v ones = {1, 1};
+    return lead + (int)__umul24((unsigned)(t >> 1), (unsigned)S) + ((t & 1) ? L - 1 : 0);  // (a frame f > 0 exists: S < 2^16)
+}
+// P of boundary (w, e) from its half-word q (elements 16 (e > 16) + 0 .. 15 of the word): the kept
+// elements -- [0, e) or [e, 32), and the clip's own [lead, lead + n) only -- as 0 / 1 weights per
+// sample pair (bits 2j and 2j + 1 of the range mask M are bits 0 and 16 of (M | M << 15) >> 2j), sum k by
+// v_dot2 with the weights, the squares of two weighted pairs chained in one 32-bit v_dot2 (as R1's
+// interior words: 4 x 32768^2 = 2^32 wraps only when all four samples are -32768, so a clip
+// holding a -32768 sample (kneg, clip-uniform) adds every pair's squares to the 64-bit sum on its own)
+typedef unsigned short ushort2v __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void partial_moments_half(const short8 (&q)[2], int w, int e, int lead, int n, bool kneg,
+                                                     int &p1, unsigned long long &p2)
+{
+    const bool hi = e > 16;
+    const int r0 = w == 0 ? lead : 0, r1 = min(lead + n - 32 * w, 32);  // the word's real elements [r0, r1), lead < 8
+    const int a = hi ? e - 16 : r0, b = hi ? min(max(r1 - 16, 0), 16) : min(e, r1);
+    const uint32_t M = ((1u << b) - 1u) & ~((1u << a) - 1u);  // elements [a, b) of the half (none: b <= a)
+    const uint32_t X = M | (M << 15);
     int s1 = 0;
     unsigned long long s2 = 0;
 #pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const uint32_t Mk = M >> (8 * k);
+    for (int k = 0; k < 2; k++) {
         short2v dm[4];
 #pragma unroll
-        for (int h = 0; h < 4; h++) {  // pair 4k + h: elements 8k + 2h, 8k + 2h + 1
-            const uint32_t b0 = (uint32_t)__builtin_amdgcn_sbfe((int)Mk, 2 * h, 1);
-            const uint32_t b1 = (uint32_t)__builtin_amdgcn_sbfe((int)Mk, 2 * h + 1, 1);
-            const uint32_t m = (b0 & 0x0000FFFFu) | (b1 & 0xFFFF0000u);
-            dm[h] = __builtin_bit_cast(short2v, __builtin_bit_cast(uint32_t, half_pair(q[k], h)) & m);
-            s1 = __builtin_amdgcn_sdot2(dm[h], ones, s1, false);
+        for (int h = 0; h < 4; h++) {  // pair 4k + h: elements 8k + 2h, 8k + 2h + 1 of the half
+            const uint32_t wt = (X >> (8 * k + 2 * h)) & 0x00010001u;
+            const short2v d = half_pair(q[k], h);
+            s1 = __builtin_amdgcn_sdot2(d, __builtin_bit_cast(short2v, wt), s1, false);
+            dm[h] = __builtin_bit_cast(short2v, __builtin_bit_cast(ushort2v, d) * __builtin_bit_cast(ushort2v, wt));
         }
         if (kneg) {
 #pragma unroll
@@ -464,8 +483,8 @@ __device__ __forceinline__ void partial_moments_fast(const short8 (&q)[4], int e
             s2 += (unsigned)sq2acc(dm[3], sq2(dm[2]));
         }
     }
-    t1 += s1;
-    t2 += s2;
+    p1 = s1;
+    p2 = s2;
 }
 
 // values every lane holds alike (read from LDS, say): pinned to scalar registers
@@ -764,40 +783,44 @@ __device__ __forceinline__ void p90_select_wave(const Ctx &c, int nv, int lane)
     }
 }
 
-// the partial word endpoint pass A needs for frame end t = tid (FAST layout: one frame end per
-// thread), issued early so that it is in flight across a barrier; past the range it reads zeros
-__device__ __forceinline__ int vad_partial_issue(const ExtractParams &p, const ClipRef &cur, int L, int S, int nv,
-                                                 int t, short8 (&qa)[4], int &e0, int &e1)
+// the half-word pass A sums for frame end t = tid (FAST layout: one frame end per thread; see
+// frame_end_pos), issued early so that it is in flight across R2 and its barrier: two 16-B loads;
+// nothing (an offset past the range, which reads zeros) for an aligned boundary and past the last
+// frame (live: t < 2 nv)
+__device__ __forceinline__ int vad_partial_issue(const ExtractParams &p, const ClipRef &cur, int L, int S, bool live,
+                                                 int t, short8 (&qa)[2])
 {
-    const int pw = vad_partial_word(cur, L, S, nv, t, e0, e1);
+    const int x = frame_end_pos(cur.lead, L, S, t);
+    const int h = t & 1, e = (x & 31) + h;
     const __amdgpu_buffer_rsrc_t rs = clip_rsrc(p, cur);
-    const int off = pw >= 0 ? 64 * pw : 0x40000000;
+    const int off = (!live || e == 32 * h) ? 0x40000000 : 2 * (x & ~31) + (e > 16 ? 32 : 0);
 #pragma unroll
-    for (int k = 0; k < 4; k++)
+    for (int k = 0; k < 2; k++)
         qa[k] = __builtin_bit_cast(short8, __builtin_amdgcn_raw_buffer_load_b128(rs, off + 16 * k, 0, 0));
-    return pw;
+    return x;
 }
 
 // VAD frames, FAST layout (nv <= 128 <= NT / 2): one lane pair per frame -- lane h of pair f owns
-// frame end t = 2f + h = tid (its partial word qa issued by vad_partial_issue), adds that word's
-// exact moments, and half of the interior word sums and of the sign changes; no pass-A barrier.
-// Frame f = buffer samples [u0, u0 + L): exact moments (wS1/wS2 words + the partial words at its
-// ends), sign changes from the positive bits -> c.vE / c.vZ.
+// frame end t = 2f + h = tid (at pa_x, its half-word qa issued by vad_partial_issue): it sums half
+// of the frame's word totals and of its sign changes, and takes off what its end's word holds
+// outside the frame (Lo or H, see frame_end_pos); no pass-A barrier.  The 64-bit sum k^2 is
+// unsigned: a lane's own difference may wrap, the pair's sum (< 2^42) is exact modulo 2^64.
+// Frame f = buffer samples [u0, u0 + L): exact moments, sign changes from the positive bits
+// -> c.vE / c.vZ.
 __device__ __forceinline__ void vad_frames_fast(const Ctx &c, const ClipRef &cur, int L, int S, const ClipStats &cs,
-                                                const short8 (&qa)[4], int pa_w, int pa_e0, int pa_e1, int tid)
+                                                const short8 (&qa)[2], int pa_x, int tid)
 {
-    const int nv = cs.nv, lead = cur.lead;
+    const int nv = cs.nv;
     const int f = tid >> 1, lh = tid & 1;
     const bool act = f < nv;
     int s1 = 0;
     unsigned long long s2 = 0;
     int zc = 0;
     if (act) {
-        const int u0 = lead + f * S, u1 = u0 + L;
+        const int u0 = lh ? pa_x - (L - 1) : pa_x, u1 = u0 + L;
         const int wa = u0 >> 5, wb = (u1 - 1) >> 5;
-        const int wi0 = (u0 & 31) ? wa + 1 : wa, wi1 = (u1 & 31) ? wb - 1 : wb;
-        const int per = (wi1 - wi0 + 2) >> 1;
-        const int ws = wi0 + lh * per, we = min(ws + per - 1, wi1);
+        const int per = (wb - wa + 2) >> 1;
+        const int ws = wa + lh * per, we = min(ws + per - 1, wb);
 #pragma unroll 4
         for (int w = ws; w <= we && !(DSP_ABL & 32); w++) {
             s1 += c.wS1[w];
@@ -805,9 +828,20 @@ __device__ __forceinline__ void vad_frames_fast(const Ctx &c, const ClipRef &cur
         }
         // sign changes at pairs [u0, u1 - 1) from R2's segment prefixes (lane 0 of the pair)
         zc = (lh || (DSP_ABL & 32)) ? 0 : zseg_count(c.posw, c.zw, c.ztot, u0, u1 - 1);
-        // the partial word last: its load (issued before the R2 barrier) lands while the LDS
-        // sums above run
-        if (pa_w >= 0 && !(DSP_ABL & 8)) partial_moments_fast(qa, pa_e0, pa_e1, cs.kneg, s1, s2);
+        // the half-word last: its load (issued before the R2 barrier) lands while the LDS sums
+        // above run
+        if (!(DSP_ABL & 8)) {
+            const int w = lh ? wb : wa, e = (pa_x & 31) + lh;
+            int p1;
+            unsigned long long p2;
+            partial_moments_half(qa, w, e, cur.lead, cur.n, cs.kneg, p1, p2);
+            if ((e > 16) != (bool)lh) {  // the start's high half (H) / the end's low half (Lo): the other part
+                p1 = c.wS1[w] - p1;
+                p2 = c.wS2[w] - p2;
+            }
+            s1 -= p1;
+            s2 -= p2;
+        }
     }
     s1 += dpp_i(s1, DPP_QXOR1);
     {
@@ -1312,11 +1346,19 @@ __device__ __forceinline__ bool clip_fast(const ExtractParams &p, const Ctx &c, 
             if (w < nword && w > 0 && w < nword - 1) r1_redo_s2(&regs[4 * r], w, c.wS2);
         }
     }
-    // then the partial word of the frame end this thread sums in pass A (one frame end per thread),
-    // re-read from L2 and issued before the barrier so that it is in flight while the workgroup
-    // synchronises.  Issued earlier, with the clip's words still live, it costs spills whose
-    // reloads wait for it: at the end of R1 3.38 ms, before R2 3.18, after R2 2.82
-    // (profiles/r05h_ab.txt, r05i_ab.txt)
+    // then the half-word of the frame end this thread sums in pass A (one frame end per thread),
+    // re-read from L2 or beyond and issued here, ahead of the sign bits, so that its round trip runs
+    // beside R2 and its barrier: pass A waits for it on the workgroup's critical path.  Two loads
+    // (8 VGPRs) fit beside the clip's words; the whole word's four did not -- their spills' reloads
+    // waited for them: at the end of R1 3.38 ms, before R2 3.18, after R2 2.82 (profiles/r05h_ab.txt,
+    // r05i_ab.txt).  The half-word after R2, where the word was issued: 2.255 against 2.229 ms here;
+    // after the R1 barriers or before them: 2 VGPR spills (profiles/passa_half_ab.txt)
+    MARK(paissue);
+    short8 qa[2];
+    int pa_x = 0;
+    if (64 * wid < 2 * nv)  // waves holding frame ends (2 nv <= 256: waves 0-3)
+        pa_x = vad_partial_issue(p, cur, L, S, tid < 2 * nv, tid, qa);
+    MARK(R2bits);
     uint32_t P[RREG];
 #pragma unroll
     for (int r = 0; r < RREG; r++) {
@@ -1328,18 +1370,13 @@ __device__ __forceinline__ bool clip_fast(const ExtractParams &p, const Ctx &c, 
     for (int r = 0; r < RREG && !(DSP_ABL & 16); r++) zseg_word(c.zw, c.ztot, P[r], r * NT + tid, lane, r * NWAVE + wid);
     if (tid < 2) c.posw[nword + tid] = 0;
     if (tid == 0) c.zw[RREG * NT] = 0;  // (a range ending at the last register word's end)
-    MARK(paissue);
-    short8 qa[4];
-    int pa_e0 = 0, pa_e1 = 0, pa_w = -1;
-    if (64 * wid < 2 * nv)  // waves holding frame ends (2 nv <= 256: waves 0-3)
-        pa_w = vad_partial_issue(p, cur, L, S, nv, tid, qa, pa_e0, pa_e1);
     __syncthreads();
     STAMP(i, 2);
 
     // ---- R3: endpoint detection (:161-273) ------------------------------------------------
     MARK(passAB);
     if (nv > 0) {
-        vad_frames_fast(c, cur, L, S, cs, qa, pa_w, pa_e0, pa_e1, tid);
+        vad_frames_fast(c, cur, L, S, cs, qa, pa_x, tid);
         STAMP(i, 7);
         __syncthreads();
         STAMP(i, 8);
