@@ -57,20 +57,17 @@
 #include <algorithm>
 
 #include "csr_pairs.h"
+#include "dhmm_internal.h"
 #include "dsp_audiorec.h"
 #include "dtw_internal.h"
 
 namespace dsp {
 
-static constexpr int DHMM_SMAX = 32;                 // states a lane keeps in registers at most
-static constexpr int DHMM_KMAX = 256;                // symbols of the alphabet at most
 static constexpr int64_t DHMM_CMAX = 1 << 20;        // models in a set at most
 static constexpr int DHMM_GCHUNK = 1024;             // models per launch at most
 static constexpr size_t DHMM_WAVE_CAP = 256u << 20;  // bytes of direction words per launch
 static constexpr int DHMM_BATCH = 16;                // members whose loads a totals thread keeps in flight
 
-// register slots of a launch: the smallest of 8, 16, 32 that holds Smax
-static inline int dhmm_slots(int Smax) { return Smax <= 8 ? 8 : (Smax <= 16 ? 16 : 32); }
 // doubles of one model's record: [K][NS] emissions, then [NS][2] (stay, adv[s-1])
 static inline size_t dhmm_record(int K, int NS) { return (size_t)K * NS + 2 * (size_t)NS; }
 // bytes between two symbols' slots in LDS: an odd number of 16-byte units (NS is a multiple of 4)

@@ -42,6 +42,7 @@ EXPORTS = ("dsp_extract_lds_bytes", "dsp_extract_fast_layout", "dsp_extract_feat
            "dsp_hmm_workspace_bytes", "dsp_hmm_score", "dsp_hmm_align", "dsp_hmm_accumulate",
            "dsp_vq_workspace_bytes", "dsp_vq_score", "dsp_vq_assign", "dsp_vq_accumulate",
            "dsp_dhmm_workspace_bytes", "dsp_dhmm_score", "dsp_dhmm_align", "dsp_dhmm_accumulate",
+           "dsp_dhmm_decode_workspace_bytes", "dsp_dhmm_decode",
            "dsp_pitch_workspace_bytes", "dsp_pitch_track", "dsp_lpc_workspace_bytes", "dsp_lpc_autocorr",
            "dsp_lpc_solve")
 DSP_WAV_OTHER, DSP_WAV_S16_MONO, DSP_WAV_U8_MONO = 0, 1, 2
@@ -192,6 +193,11 @@ def load_library(path=LIB_PATH):
         L.dsp_dhmm_align.argtypes = model + syms + [vp, vp, i64, vp, vp, vp, sz, vp]
         L.dsp_dhmm_accumulate.restype = i32
         L.dsp_dhmm_accumulate.argtypes = [vp, i64, i32, i32] + syms + [vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    if hasattr(L, "dsp_dhmm_decode"):  # (older A/B variants lack the connected-word decoder)
+        L.dsp_dhmm_decode_workspace_bytes.restype = sz
+        L.dsp_dhmm_decode_workspace_bytes.argtypes = [i64, i64, i32, i32, i32]
+        L.dsp_dhmm_decode.restype = i32  # emit, stay, adv, n_states, enter, C, Smax, K, sym, len, N, T, max_words, outputs
+        L.dsp_dhmm_decode.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, vp, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]
     if hasattr(L, "dsp_pitch_track"):  # (older A/B variants lack the pitch track)
         L.dsp_pitch_workspace_bytes.restype = sz
         L.dsp_pitch_workspace_bytes.argtypes = [i32, i64, i32, i32, i32, i32]

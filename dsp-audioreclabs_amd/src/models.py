@@ -639,6 +639,45 @@ class DiscreteHmmClassifier(SequenceClassifier):
             raise ValueError("sequence %d has fewer frames than every model has states" % int(np.argmax(label < 0)))
         return self.classes_[label]
 
+    def decode(self, X, lengths=None, word_penalty=0.0, max_words=None):
+        """Connected words: each utterance of X is several words in a row with unknown boundaries, decoded by
+        the one-pass Viterbi over a loop of the class models (csrc/dhmm_decode.hip, dsp_dhmm_decode, DESIGN.md
+        §4.15; at most ``pipeline.DHMM_DECODE_MAX_MODELS`` classes).  The frames are tokenised exactly as
+        ``predict`` does.  ``word_penalty``: the cost of starting a word, a scalar or one value per class.
+        Returns (labels, starts): per utterance the class labels of its words in time order and their first
+        frames, both empty for an utterance no word sequence fits."""
+        from .pipeline import dhmm_decode
+        Xq, nq = _as_padded(X, lengths)
+        if Xq.shape[2] != self.tokenizer_.codebook_.shape[1]:
+            raise ValueError("X has %d feature channels, the fitted codebook %d"
+                             % (Xq.shape[2], self.tokenizer_.codebook_.shape[1]))
+        sym = self.tokenizer_.transform(self._scale(Xq, nq), nq)
+        _, n_words, words, start, _ = dhmm_decode(self.model_, sym, nq, enter=word_penalty, max_words=max_words)
+        n_words, words, start = (t.cpu().numpy() for t in (n_words, words, start))
+        kept = np.minimum(n_words, words.shape[1])
+        return ([self.classes_[words[i, :kept[i]]] for i in range(len(kept))],
+                [start[i, :kept[i]].copy() for i in range(len(kept))])
+
+
+def word_error_rate(ref, hyp):
+    """(substitutions + deletions + insertions) / reference words over paired lists of label sequences: the
+    plain Levenshtein distance of each pair, summed, over the summed reference lengths (host only)."""
+    if len(ref) != len(hyp):
+        raise ValueError("%d reference sequences for %d hypotheses" % (len(ref), len(hyp)))
+    errors = total = 0
+    for r, h in zip(ref, hyp):
+        r, h = list(r), list(h)
+        row = list(range(len(h) + 1))
+        for i in range(1, len(r) + 1):
+            diag, row[0] = row[0], i
+            for j in range(1, len(h) + 1):
+                diag, row[j] = row[j], min(row[j] + 1, row[j - 1] + 1, diag + (r[i - 1] != h[j - 1]))
+        errors += row[len(h)]
+        total += len(r)
+    if total == 0:
+        raise ValueError("the reference holds no word")
+    return errors / total
+
 
 # ==================== MLP (models.py:77-221) ====================
 

@@ -993,6 +993,49 @@ def dhmm_align(models, sym, lengths, groups=None, assign=None, with_seg=True):
     return score, seg, up.start, up.members
 
 
+DHMM_DECODE_MAX_MODELS = 64  # word models of a decoding loop at most (csrc/dhmm_decode.hip: a lane per model)
+
+
+def dhmm_decode(models, sym, lengths, enter=None, max_words=None):
+    """Connected-word decoding (include/dsp_audiorec.h: dsp_dhmm_decode): the one-pass Viterbi of the
+    symbol rows sym int32 [N, T] over a loop of the models of the ``DhmmModelSet`` (at most
+    ``DHMM_DECODE_MAX_MODELS``).  ``enter``: the cost of starting a word, None (0.0), a scalar or one value
+    per model, finite or +inf.  ``max_words``: the words kept per utterance, T when None.  Returns (score
+    float64 [N], n_words int32 [N], words int32 [N, max_words], start int32 [N, max_words], cum float64
+    [N, max_words]) on the device; -1 (cum: +inf) behind an utterance's words."""
+    import torch
+    d = _hip.require_device()
+    s, n = _dhmm_operand(sym, lengths, d)
+    N, T = s.shape
+    margs = _dhmm_model_args(models, d)
+    C, Smax, K = margs[-3:]
+    if not 1 <= C <= DHMM_DECODE_MAX_MODELS:
+        raise ValueError("a decoding loop takes 1 .. %d word models, got %d" % (DHMM_DECODE_MAX_MODELS, C))
+    if T < 1:
+        raise ValueError(_DHMM_SHAPE)
+    max_words = T if max_words is None else int(max_words)
+    if not 1 <= max_words <= T:
+        raise ValueError("max_words must lie in [1, T = %d]" % T)
+    cost = None
+    if enter is not None:
+        cost = np.array(np.broadcast_to(np.asarray(_as_host(enter), np.float64), (C,)))
+        if np.isnan(cost).any() or (cost == -np.inf).any():
+            raise ValueError("enter must be finite or +inf")
+        cost = _as_device(cost, torch.float64, d)
+    score = torch.empty(N, dtype=torch.float64, device=d)
+    n_words = torch.empty(N, dtype=torch.int32, device=d)
+    words = torch.empty((N, max_words), dtype=torch.int32, device=d)
+    start = torch.empty((N, max_words), dtype=torch.int32, device=d)
+    cum = torch.empty((N, max_words), dtype=torch.float64, device=d)
+    if N > 0:
+        ws = _grown(None, _hip.lib().dsp_dhmm_decode_workspace_bytes(C, N, T, Smax, K), _DHMM_SHAPE, d)
+        rc = _hip.lib().dsp_dhmm_decode(*margs[:4], _hip.ptr(cost), C, Smax, K, _hip.ptr(s), _hip.ptr(n), N, T, max_words,
+                                        _hip.ptr(score), _hip.ptr(n_words), _hip.ptr(words), _hip.ptr(start), _hip.ptr(cum),
+                                        _hip.ptr(ws), ws.numel(), _hip.stream_handle(d))
+        _hip.check(rc, "dsp_dhmm_decode")
+    return score, n_words, words, start, cum
+
+
 class VqTokenizer:
     """ONE vector-quantisation codebook shared by all sequences: the tokeniser in front of the discrete
     HMMs.  ``fit`` trains it by LBG binary splitting on all sequences together -- by definition the

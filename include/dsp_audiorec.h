@@ -36,7 +36,7 @@ extern "C" {
                               5: queue_ws is 4 KiB (each counter on its own 256-B line);
                               6: the extraction entry points take out_stride (packed result rows);
                                  dsp_knn_classify takes flags (DSP_KNN_REF_READY).
-                              Still 6 with the dsp_mlp_*, dsp_svc_*, dsp_gnb_*, dsp_tree_* and dsp_dtw_* (dsp_dtw_align, dsp_dtw_dba_update included) and dsp_hmm_* and dsp_vq_* and dsp_dhmm_* and dsp_pitch_* and dsp_lpc_* entry points: new symbols only, no
+                              Still 6 with the dsp_mlp_*, dsp_svc_*, dsp_gnb_*, dsp_tree_* and dsp_dtw_* (dsp_dtw_align, dsp_dtw_dba_update included) and dsp_hmm_* and dsp_vq_* and dsp_dhmm_* (dsp_dhmm_decode included) and dsp_pitch_* and dsp_lpc_* entry points: new symbols only, no
                               existing signature or meaning changed, so callers built against 6 keep
                               working (a binding that needs them checks for the symbols) */
 
@@ -712,6 +712,55 @@ int dsp_dhmm_accumulate(const int32_t *n_states, int64_t C, int Smax, int K, con
                         int64_t N, int T, const int32_t *group_start, const int32_t *members, int64_t P,
                         const int32_t *seg, const double *score, int32_t *cnt_emit, int32_t *cnt, int32_t *n_valid,
                         double *total, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Connected-word decoding: the one-pass (token-passing) Viterbi over a loop of the word models of a
+ * dsp_dhmm_* set.  An utterance holds several words in a row with unknown boundaries; the result is the
+ * word sequence.  csrc/dhmm_decode.hip, DESIGN.md §4.15.  Bit for bit like the entry points above: fp64
+ * add and compare only, each operation rounded.
+ *
+ * Inputs.  The model set of dsp_dhmm_score with the same value rules: emit float64 [C, Smax, K], stay,
+ *   adv float64 [C, Smax], n_states int32 [C]; adv[c, S-1] stays unread: leaving a word's last state is
+ *   free.  enter float64 [C] is the cost of starting word c (a word penalty plus, if the caller wants,
+ *   -log of a prior): finite or +inf, never NaN, never -inf; NULL means all 0.0.  A model with
+ *   n_states[c] outside 1 .. Smax counts as enter[c] = +inf: it is never entered and never read.
+ *   1 <= C <= 64 (DSP_DHMM_DECODE_MAX_MODELS), Smax <= 32, K <= 256.  sym int32 [N, T], len int32 [N],
+ *   T <= 1024, as for dsp_dhmm_score.
+ * Recurrence.  For an utterance of n frames every cell is (V, start), with V(-1, ., .) = +inf and
+ *   X(-1) = 0.0.  For t = 0 .. n-1, model c with S = n_states[c], state s:
+ *     e = emit[c, s, sym[t]]
+ *     a = V(t-1,c,s) + stay[c,s]
+ *     b = s > 0 ?  V(t-1,c,s-1) + adv[c,s-1]  :  X(t-1) + enter[c]
+ *     advance iff b < a (strictly; ties stay)
+ *     V(t,c,s)     = e + (advance ? b : a)
+ *     start(t,c,s) = advance ? (s > 0 ? start(t-1,c,s-1) : t) : start(t-1,c,s)
+ *     X(t) = min over c ascending of V(t,c,S_c-1), a later c replacing only if strictly smaller
+ *     W(t) = that c (-1 when every exit is +inf)
+ *     B(t) = start(t, W(t), S_W-1)
+ * Result.  score = X(n-1).  The words are walked back: t = n-1; the word is W(t) and it starts at B(t);
+ *   then t = B(t) - 1, until t < 0.  Outputs, in time order:
+ *     score    float64 [N]             X(n-1)
+ *     n_words  int32 [N]               the true number of words
+ *     words    int32 [N, max_words]    the word models in time order
+ *     start    int32 [N, max_words]    first frame of each word
+ *     cum      float64 [N, max_words]  X at each word's last frame, so the last one is score
+ *   With more than max_words words the first max_words in time order are written; 1 <= max_words <= T.
+ *   Entries behind the words are -1 (cum: +inf).  score is +inf, n_words 0 and the rows -1 / +inf when
+ *   n < 1 or n > T, when any sym[t], t < n, lies outside [0, K) (such a symbol never indexes a table), and
+ *   when no word can end at n-1.  Any output may be NULL.
+ * workspace  device scratch of dsp_dhmm_decode_workspace_bytes(C, N, T, Smax, K) bytes (0: sizes outside
+ *   the plan): the set transposed to one 512-byte line per (symbol, state slot) across the 64 models, the
+ *   transitions and entry costs per slot.  Nothing in it is carried from one call to the next.
+ * dsp_dhmm_decode checks its host arguments before any launch (DSP_ERR_ARGS, DSP_ERR_WORKSPACE), returns
+ * DSP_OK with nothing to do (N = 0, every output NULL), makes no host synchronisation and no allocation,
+ * and writes only to its outputs and the workspace, on the caller's stream.
+ */
+#define DSP_DHMM_DECODE_MAX_MODELS 64
+size_t dsp_dhmm_decode_workspace_bytes(int64_t C, int64_t N, int T, int Smax, int K);
+int dsp_dhmm_decode(const double *emit, const double *stay, const double *adv, const int32_t *n_states,
+                    const double *enter, int64_t C, int Smax, int K, const int32_t *sym, const int32_t *len, int64_t N,
+                    int T, int max_words, double *score, int32_t *n_words, int32_t *words, int32_t *start, double *cum,
+                    void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * Short-time autocorrelation pitch track -- the fourth classical time-domain feature next to energy,
