@@ -44,7 +44,7 @@ def load_both_methods(data_dir=None, frame_length=None, frame_shift=None, window
 
 
 def compare(data_dir=None, classifiers=None, test_size=0.2, random_state=42, dtw=False, dtw_template=False,
-            hmm=False, pitch=False, lpc=0, vq=False, dhmm=False):
+            hmm=False, pitch=False, lpc=0, vq=False, dhmm=False, dhmm_bw=False):
     """:124-214: each classifier on both feature sets, the reference's split and normalisation
     -> {classifier: {'statistical': acc, 'sequence': acc, 'diff': sequence - statistical}}.
     KNN on the flattened sequences (2 x max_frames columns) runs on the device like the 15-d
@@ -60,6 +60,8 @@ def compare(data_dir=None, classifiers=None, test_size=0.2, random_state=42, dtw
     per class (src.models.VqClassifier, its defaults).
     dhmm=True (an extension) adds the row 'VQ-HMM' after 'VQ': the same, for one discrete-observation HMM per
     class over one shared codebook (src.models.DiscreteHmmClassifier, its defaults).
+    dhmm_bw=True (an extension) adds the row 'VQ-HMM (BW)' after it: the same classifier with Baum-Welch
+    training and forward scoring (training='baum_welch', scoring='forward').
     pitch=True (an extension): every row runs on the 20-d matrix (the 15 columns plus five f0 statistics)
     and on the (E, ZCR, f0) sequences of the exact autocorrelation pitch track (src.pipeline.PitchTracker).
     lpc=n (an extension): the n LPC cepstra of every frame join the sequences and their means and standard
@@ -68,7 +70,7 @@ def compare(data_dir=None, classifiers=None, test_size=0.2, random_state=42, dtw
     from sklearn.model_selection import train_test_split
     if isinstance(lpc, bool) or int(lpc) != lpc or not 0 <= lpc <= 64:
         raise ValueError("lpc is the number of cepstra per frame, 0 .. 64")
-    if (dtw or dtw_template or hmm or vq or dhmm) and 2 + bool(pitch) + lpc > 8:
+    if (dtw or dtw_template or hmm or vq or dhmm or dhmm_bw) and 2 + bool(pitch) + lpc > 8:
         raise ValueError("the DTW and HMM rows take sequences of at most 8 channels: E, ZCR%s and %d cepstra are %d"
                          % (", f0" if pitch else "", lpc, 2 + bool(pitch) + lpc))
     X_stat, X_seq, y, lengths = load_both_methods(data_dir, pitch=pitch, lpc=lpc)
@@ -89,7 +91,7 @@ def compare(data_dir=None, classifiers=None, test_size=0.2, random_state=42, dtw
             acc[method] = float(clf.evaluate(te, y_te)['accuracy'])
         results[name] = {'statistical': acc['statistical'], 'sequence': acc['sequence'],
                          'diff': acc['sequence'] - acc['statistical']}
-    if dtw or dtw_template or hmm or vq or dhmm:
+    if dtw or dtw_template or hmm or vq or dhmm or dhmm_bw:
         tr, te = train_test_split(np.arange(len(y)), test_size=test_size, random_state=random_state, stratify=y)
         lengths = np.asarray(lengths)
         if 'KNN' in results:
@@ -102,7 +104,8 @@ def compare(data_dir=None, classifiers=None, test_size=0.2, random_state=42, dtw
                ([('DTW-template', 'dtw_template', {})] if dtw_template else []) + \
                ([('HMM', 'hmm', {})] if hmm else []) + \
                ([('VQ', 'vq', {})] if vq else []) + \
-               ([('VQ-HMM', 'dhmm', {})] if dhmm else [])
+               ([('VQ-HMM', 'dhmm', {})] if dhmm else []) + \
+               ([('VQ-HMM (BW)', 'dhmm', {'training': 'baum_welch', 'scoring': 'forward'})] if dhmm_bw else [])
         for name, kind, params in rows:
             clf = create_classifier(kind, **params).fit(X_seq[tr], y[tr], lengths=lengths[tr])
             seq_acc = float(clf.evaluate(X_seq[te], y[te], lengths=lengths[te])['accuracy'])

@@ -554,20 +554,36 @@ class DiscreteHmmClassifier(SequenceClassifier):
     alpha        the additive smoothing of the emission tables (> 0), see ``pipeline.DhmmModelSet``.
     trans_floor  p_stay is clamped to [trans_floor, 1 - trans_floor].
     vq_iter, eps the tokeniser's Lloyd rounds per level and its split offset (``VqClassifier``'s n_iter, eps).
+    training     'viterbi' (hard counts along the best path, the default) or 'baum_welch': soft counts, the
+                 state posteriors of the forward-backward pass (csrc/dhmm_fb.hip, dsp_dhmm_expect, DESIGN.md
+                 §4.16).  After the same uniform start, exactly ``n_iter`` rounds of expect -> rebuild
+                 (``pipeline.DhmmProbSet``); there is no early stop.
+    scoring      'viterbi' (the best path's cost, the default) or 'forward': the likelihood summed over all
+                 paths (dsp_dhmm_forward); ``score_samples`` then returns ``pipeline.dhmm_nll`` and ``predict``
+                 the label the device decides by exact comparison.  ``decode`` always uses ``model_``.
     ``fit``: the training set, the tokeniser's fit and transform on the scaled training set, the uniform
     segmentation, one accumulate, then the rounds.  A training sequence shorter than its class's n_states
     is left out of that class's statistics; a class none of whose members is long enough raises ValueError.
     ``predict`` raises ValueError for a query with fewer frames than every model has states
     (``score_samples`` returns its row of +inf).
     After ``fit``: tokenizer_ (``pipeline.VqTokenizer``), model_ (``pipeline.DhmmModelSet``: emit, stay, adv,
-    n_states), totals_ float64 [rounds run, C], n_iter_ the rounds run.
+    n_states), totals_ float64 [rounds run, C], n_iter_ the rounds run.  With training='baum_welch' or
+    scoring='forward' also prob_ (``pipeline.DhmmProbSet``); Baum-Welch training sets model_ =
+    prob_.to_costs() and totals_ to the per-class sums of ``dhmm_nll`` over the members with a non-zero
+    likelihood, added in list order on the host; after Viterbi training prob_ is built from the same counts as
+    model_ round by round by ``DhmmProbSet``'s formulas (``prev=`` included), so it holds the same models.
     No CPU path: ``fit`` and ``predict`` raise HipError without a HIP device (constructing needs none).
     """
 
     def __init__(self, n_states=5, n_codes=64, n_iter=10, alpha=0.5, trans_floor=1e-3, vq_iter=10, eps=0.01,
-                 normalize=True):
+                 normalize=True, training='viterbi', scoring='viterbi'):
         super().__init__(n_neighbors=1, window=None, normalize=normalize)
         from .pipeline import HMM_MAX_STATES, VqTokenizer
+        if training not in ('viterbi', 'baum_welch'):
+            raise ValueError("training must be 'viterbi' or 'baum_welch', got %r" % (training,))
+        if scoring not in ('viterbi', 'forward'):
+            raise ValueError("scoring must be 'viterbi' or 'forward', got %r" % (scoring,))
+        self.training, self.scoring = training, scoring
         states = np.asarray(n_states)
         if states.ndim > 1 or states.size < 1 or not np.issubdtype(states.dtype, np.integer):
             raise ValueError("n_states must be an int or one int per class")
@@ -583,7 +599,8 @@ class DiscreteHmmClassifier(SequenceClassifier):
             raise ValueError("trans_floor must lie in (0, 0.5)")
 
     def fit(self, X, y, lengths=None):
-        from .pipeline import DhmmModelSet, DhmmUpdater, VqTokenizer, hmm_uniform_segmentation
+        from .pipeline import (DhmmModelSet, DhmmProbSet, DhmmUpdater, VqTokenizer, dhmm_nll,
+                               hmm_uniform_segmentation)
         X, n, codes = self._training_set(X, y, lengths)
         C, K = len(self.classes_), self.n_codes
         states = np.full(C, self.n_states, np.int32) if np.ndim(self.n_states) == 0 else self.n_states
@@ -600,13 +617,30 @@ class DiscreteHmmClassifier(SequenceClassifier):
         updater = DhmmUpdater(self.tokenizer_.transform(X, n), n, start, order)
         seg = hmm_uniform_segmentation(n[order], states[codes[order]], Smax)
         stats = updater.accumulate(states, K, seg, np.zeros(len(order)))
+        if self.training == 'baum_welch':
+            prob = DhmmProbSet(stats[0], stats[2], states, self.alpha, self.trans_floor)
+            totals = np.zeros((self.n_iter, C))
+            for it in range(self.n_iter):
+                mant, expo, occ_emit, n_valid = updater.expect(prob)
+                nll = dhmm_nll(mant, expo)
+                for c in range(C):  # list order, from 0.0
+                    for v in nll[start[c]:start[c + 1]]:
+                        if v < np.inf:
+                            totals[it, c] += v
+                prob = DhmmProbSet(occ_emit, n_valid, states, self.alpha, self.trans_floor, prev=prob)
+            self.prob_, self.model_, self.n_iter_, self.totals_ = prob, prob.to_costs(), self.n_iter, totals
+            return self
         model = DhmmModelSet(*stats[:3], states, self.alpha, self.trans_floor)
+        forward = self.scoring == 'forward'  # then prob_ follows model_ round by round, prev= included
+        prob = DhmmProbSet(stats[0], stats[2], states, self.alpha, self.trans_floor) if forward else None
         totals = []
         for _ in range(self.n_iter):
             score, new_seg = updater.align(model)
             stats = updater.accumulate(states, K, new_seg, score)
             totals.append(stats[3].cpu().numpy())
             model = DhmmModelSet(*stats[:3], states, self.alpha, self.trans_floor, prev=model)
+            if forward:
+                prob = DhmmProbSet(stats[0], stats[2], states, self.alpha, self.trans_floor, prev=prob)
             new_seg = new_seg.cpu().numpy()
             same = np.array_equal(new_seg, seg)
             seg = new_seg
@@ -614,21 +648,29 @@ class DiscreteHmmClassifier(SequenceClassifier):
                 break
         self.model_, self.n_iter_ = model, len(totals)
         self.totals_ = np.array(totals, dtype=np.float64).reshape(len(totals), C)
+        if forward:
+            self.prob_ = prob
         return self
 
     def _scores(self, X, lengths, with_labels):
-        from .pipeline import dhmm_score
+        from .pipeline import dhmm_forward, dhmm_score
         Xq, nq = _as_padded(X, lengths)
         if Xq.shape[2] != self.tokenizer_.codebook_.shape[1]:
             raise ValueError("X has %d feature channels, the fitted codebook %d"
                              % (Xq.shape[2], self.tokenizer_.codebook_.shape[1]))
         sym = self.tokenizer_.transform(self._scale(Xq, nq), nq)
+        if self.scoring == 'forward':
+            out = dhmm_forward(self.prob_, sym, nq, with_labels=with_labels)
+            return (out[0], out[1]), (out[2] if with_labels else None)
         return dhmm_score(self.model_, sym, nq, with_labels=with_labels)
 
     def score_samples(self, X, lengths=None):
-        """float64 [n, C]: each sequence's negative log-likelihood along its best state path under each
-        class's model (+inf where the sequence has fewer frames than the model has states)."""
-        return self._scores(X, lengths, False)[0].cpu().numpy()
+        """float64 [n, C]: each sequence's negative log-likelihood under each class's model, along its best
+        state path (scoring='viterbi') or summed over all paths (scoring='forward'); +inf where the sequence
+        has fewer frames than the model has states."""
+        from .pipeline import dhmm_nll
+        score = self._scores(X, lengths, False)[0]
+        return dhmm_nll(*score) if self.scoring == 'forward' else score.cpu().numpy()
 
     def kneighbors(self, X, lengths=None):
         raise NotImplementedError("an HMM classifier keeps no training sequences")

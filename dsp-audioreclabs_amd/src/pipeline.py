@@ -876,6 +876,91 @@ class DhmmModelSet:
         return self._dev
 
 
+DHMM_MIN_PROB = 2.0 ** -300  # the smallest non-zero probability dsp_dhmm_forward reads (include/dsp_audiorec.h)
+
+
+class DhmmProbSet:
+    """The model set of ``DhmmModelSet`` in the PROBABILITY domain, in the form ``dsp_dhmm_forward`` and
+    ``dsp_dhmm_expect`` read (include/dsp_audiorec.h): pemit float64 [C, Smax, K], pstay, padv float64
+    [C, Smax] and n_states int32 [C], numpy arrays on the host, built from the expected counts of
+    ``dsp_dhmm_expect`` (or from the integer counts of ``dsp_dhmm_accumulate``, taken as they are):
+        occ[c, s] = occ_emit[c, s, :] added sequentially in ascending k
+        pemit = (occ_emit + alpha) / (occ + alpha * K)      alpha * K one rounded product
+        pstay = (occ - n_valid) / occ, clamped to [trans_floor, 1 - trans_floor];  padv = 1.0 - pstay
+    In a left-to-right model without skips every path leaves a state exactly once, so the expected advance
+    count is n_valid: ``DhmmModelSet``'s formula with a real-valued occupancy.  pstay is 0.5 for a state
+    nothing was seen in and for a model with n_valid == 0, which keeps ``prev``'s pstay when ``prev`` is
+    given.  Rows s >= n_states[c] are zeros.  ``from_arrays`` takes a hand-built set; ``to_costs`` gives the
+    ``DhmmModelSet`` of the same models, which feeds dhmm_score, dhmm_align and dhmm_decode unchanged."""
+
+    def __init__(self, occ_emit, n_valid, n_states, alpha=0.5, trans_floor=1e-3, prev=None):
+        occ_emit = np.asarray(_as_host(occ_emit), np.float64)
+        n_valid, n_states = (_as_host(v).astype(np.int64) for v in (n_valid, n_states))
+        if occ_emit.ndim != 3:
+            raise ValueError("occ_emit must be [C, Smax, K]")
+        C, Smax, K = occ_emit.shape
+        DhmmModelSet._check(C, Smax, K, n_states)
+        if n_valid.shape != (C,):
+            raise ValueError("n_valid must be [C]")
+        if not (alpha > 0.0 and np.isfinite(alpha)):
+            raise ValueError("alpha must be a positive number")
+        if not 0.0 < trans_floor < 0.5:
+            raise ValueError("trans_floor must lie in (0, 0.5)")
+        if not (np.isfinite(occ_emit).all() and (occ_emit >= 0.0).all()):
+            raise ValueError("occ_emit must be finite and non-negative")
+        alpha = np.float64(alpha)
+        valid = np.arange(Smax)[None, :] < n_states[:, None]
+        occ = np.add.accumulate(occ_emit, axis=2)[:, :, -1]  # sequential, ascending k: np.sum adds pairwise
+        pemit = (occ_emit + alpha) / (occ + alpha * np.float64(K))[:, :, None]
+        seen = valid & (occ > 0.0) & (n_valid[:, None] > 0)
+        of = np.where(seen, occ, 2.0)
+        p = (of - np.where(seen, n_valid[:, None], 1).astype(np.float64)) / of
+        p = np.minimum(np.maximum(p, trans_floor), 1.0 - trans_floor)
+        if prev is not None:
+            p = np.where((n_valid == 0)[:, None], prev.pstay, p)
+        self.n_states = n_states.astype(np.int32)
+        self.pemit = np.where(valid[:, :, None], pemit, 0.0)
+        self.pstay, self.padv = np.where(valid, p, 0.0), np.where(valid, 1.0 - p, 0.0)
+        self._dev = None
+
+    @classmethod
+    def from_arrays(cls, pemit, pstay, padv, n_states):
+        """A hand-built set: pemit [C, Smax, K], pstay, padv [C, Smax] as they are (every entry 0.0 or in
+        [2^-300, 1], never NaN), n_states [C]."""
+        pemit, pstay, padv = (np.array(_as_host(v, np.float64)) for v in (pemit, pstay, padv))
+        n_states = _as_host(n_states).astype(np.int64).reshape(-1)
+        if pemit.ndim != 3 or pstay.shape != pemit.shape[:2] or padv.shape != pemit.shape[:2]:
+            raise ValueError("pemit must be [C, Smax, K] and pstay, padv [C, Smax]")
+        DhmmModelSet._check(*pemit.shape, n_states)
+        for v in (pemit, pstay, padv):
+            if not ((v == 0.0) | ((v >= DHMM_MIN_PROB) & (v <= 1.0))).all():
+                raise ValueError("probabilities must be 0.0 or lie in [2^-300, 1]")
+        self = cls.__new__(cls)
+        self.pemit, self.pstay, self.padv, self.n_states, self._dev = pemit, pstay, padv, n_states.astype(np.int32), None
+        return self
+
+    @property
+    def shape(self):
+        return self.pemit.shape
+
+    def on_device(self, device):
+        """(pemit, pstay, padv, n_states) as device tensors, uploaded once."""
+        import torch
+        if self._dev is None or self._dev[0].device != torch.device(device):
+            self._dev = tuple(_as_device(a, torch.float64, device) for a in (self.pemit, self.pstay, self.padv))
+            self._dev += (_as_device(self.n_states, torch.int32, device),)
+        return self._dev
+
+    def to_costs(self):
+        """The ``DhmmModelSet`` of the same models: -log p entry by entry, +inf for 0.0 (rows s >= n_states[c]
+        stay zeros)."""
+        valid = np.arange(self.shape[1])[None, :] < self.n_states[:, None]
+        with np.errstate(divide="ignore"):
+            emit, stay, adv = (-np.log(v) for v in (self.pemit, self.pstay, self.padv))
+        return DhmmModelSet.from_arrays(np.where(valid[:, :, None], emit, 0.0), np.where(valid, stay, 0.0),
+                                        np.where(valid, adv, 0.0), self.n_states)
+
+
 _DHMM_SHAPE = ("unsupported discrete HMM shape (1 <= T <= 1024, 1 <= Smax <= %d, 1 <= K <= %d)"
                % (HMM_MAX_STATES, DHMM_MAX_SYMBOLS))
 
@@ -918,6 +1003,37 @@ def dhmm_score(models, sym, lengths, with_labels=False, _ws=None):
     return score, label
 
 
+def dhmm_forward(models, sym, lengths, with_labels=False, _ws=None):
+    """Forward likelihoods (include/dsp_audiorec.h: dsp_dhmm_forward) of the symbol rows sym int32 [N, T]
+    under every model of the ``DhmmProbSet``: (mant float64 [N, C], expo int32 [N, C][, label int32 [N]]) on
+    the device.  The likelihood is mant * 2^expo, mant in [0.5, 1), or (0.0, 0) where it is zero: a sequence
+    shorter than the model, or one that holds a symbol outside the alphabet.  label: the model of the largest
+    likelihood, -1 when every likelihood is zero.  ``dhmm_nll`` turns the pairs into negative logs."""
+    import torch
+    d = _hip.require_device()
+    s, n = _dhmm_operand(sym, lengths, d)
+    N, T = s.shape
+    margs = _dhmm_model_args(models, d)
+    C, Smax, K = margs[-3:]
+    mant = torch.empty((N, C), dtype=torch.float64, device=d)
+    expo = torch.empty((N, C), dtype=torch.int32, device=d)
+    label = torch.empty(N, dtype=torch.int32, device=d) if with_labels else None
+    if N > 0:
+        ws = _grown(_ws, _hip.lib().dsp_dhmm_fb_workspace_bytes(C, N, 0, T, Smax, K), _DHMM_SHAPE, d)
+        rc = _hip.lib().dsp_dhmm_forward(*margs, _hip.ptr(s), _hip.ptr(n), N, T, _hip.ptr(mant), _hip.ptr(expo),
+                                         _hip.ptr(label), _hip.ptr(ws), ws.numel(), _hip.stream_handle(d))
+        _hip.check(rc, "dsp_dhmm_forward")
+    return (mant, expo, label) if with_labels else (mant, expo)
+
+
+def dhmm_nll(mant, expo):
+    """-(log(mant) + expo * log(2.0)) of ``dhmm_forward``'s pairs as a float64 numpy array, +inf where mant
+    == 0: the only logarithm of the forward path, taken on the host."""
+    mant, expo = np.asarray(_as_host(mant), np.float64), np.asarray(_as_host(expo)).astype(np.float64)
+    zero = mant == 0.0
+    return np.where(zero, np.inf, -(np.log(np.where(zero, 1.0, mant)) + expo * np.log(2.0)))
+
+
 class DhmmUpdater(_PairListPlan):
     """The symbol rows of a Viterbi training run uploaded once with their CSR class lists (one group per
     model): the plan's ``seqs`` is the int32 [N, T] tensor; the workspace is held across iterations.
@@ -932,7 +1048,7 @@ class DhmmUpdater(_PairListPlan):
         start, members = _dtw_groups((group_start, members), None, self.C, self.N)
         self.P = int(members.size)
         self.start, self.members = _as_device(start, torch.int32, d), _as_device(members, torch.int32, d)
-        self._ws = None
+        self._ws = self._fb_ws = None  # dsp_dhmm_workspace_bytes and dsp_dhmm_fb_workspace_bytes: each only grows
 
     def _workspace(self, Smax, K):
         return self._grow(_hip.lib().dsp_dhmm_workspace_bytes(self.C, self.N, self.P, self.T, Smax, K), _DHMM_SHAPE)
@@ -979,6 +1095,44 @@ class DhmmUpdater(_PairListPlan):
                                                 _hip.stream_handle(d))
             _hip.check(rc, "dsp_dhmm_accumulate")
         return cnt_emit, cnt, n_valid, total
+
+    def expect(self, models, with_gamma=False):
+        """The forward-backward pass of every listed pair under the ``DhmmProbSet`` (one ``dsp_dhmm_expect``
+        call): (mant float64 [P], expo int32 [P], occ_emit float64 [C, Smax, K], n_valid int32 [C][, gamma
+        float64 [P, T, Smax]]) on the device."""
+        import torch
+        d = self.device
+        margs = _dhmm_model_args(models, d)
+        C, Smax, K = margs[-3:]
+        if C != self.C:
+            raise ValueError("%d models for %d groups" % (C, self.C))
+        mant = torch.zeros(self.P, dtype=torch.float64, device=d)
+        expo = torch.zeros(self.P, dtype=torch.int32, device=d)
+        occ_emit = torch.empty((C, Smax, K), dtype=torch.float64, device=d)  # zeroed by the call itself
+        n_valid = torch.empty(C, dtype=torch.int32, device=d)
+        gamma = torch.empty((self.P, self.T, Smax), dtype=torch.float64, device=d) if with_gamma else None
+        if C > 0:
+            nbytes = _hip.lib().dsp_dhmm_fb_workspace_bytes(C, self.N, self.P, self.T, Smax, K)
+            ws = self._fb_ws = _grown(self._fb_ws, nbytes, _DHMM_SHAPE, d)
+            rc = _hip.lib().dsp_dhmm_expect(*margs, _hip.ptr(self.seqs), _hip.ptr(self.len_s), self.N, self.T,
+                                            _hip.ptr(self.start), _hip.ptr(self.members), self.P, _hip.ptr(mant),
+                                            _hip.ptr(expo), _hip.ptr(gamma), _hip.ptr(occ_emit), _hip.ptr(n_valid),
+                                            _hip.ptr(ws), ws.numel(), _hip.stream_handle(d))
+            _hip.check(rc, "dsp_dhmm_expect")
+        out = (mant, expo, occ_emit, n_valid)
+        return out + (gamma,) if with_gamma else out
+
+
+def dhmm_posterior(models, sym, lengths, groups=None, assign=None):
+    """State posteriors (include/dsp_audiorec.h: dsp_dhmm_expect) of the symbol rows sym[members[p]] under
+    model c of the ``DhmmProbSet``, the pairs given as in ``dhmm_align``.  Returns (gamma float64 [P, T, Smax],
+    group_start, members) on the device: gamma[p, t, s] the probability of state s at frame t given the whole
+    sequence and the forced start and end, zeros behind the sequence's frames and the model's states and
+    everywhere for a pair that is not valid."""
+    N = len(lengths)
+    start, members = _dtw_groups(groups, assign, models.shape[0], N)
+    up = DhmmUpdater(sym, lengths, start, members)
+    return up.expect(models, with_gamma=True)[4], up.start, up.members
 
 
 def dhmm_align(models, sym, lengths, groups=None, assign=None, with_seg=True):

@@ -36,7 +36,7 @@ extern "C" {
                               5: queue_ws is 4 KiB (each counter on its own 256-B line);
                               6: the extraction entry points take out_stride (packed result rows);
                                  dsp_knn_classify takes flags (DSP_KNN_REF_READY).
-                              Still 6 with the dsp_mlp_*, dsp_svc_*, dsp_gnb_*, dsp_tree_* and dsp_dtw_* (dsp_dtw_align, dsp_dtw_dba_update included) and dsp_hmm_* and dsp_vq_* and dsp_dhmm_* (dsp_dhmm_decode included) and dsp_pitch_* and dsp_lpc_* entry points: new symbols only, no
+                              Still 6 with the dsp_mlp_*, dsp_svc_*, dsp_gnb_*, dsp_tree_* and dsp_dtw_* (dsp_dtw_align, dsp_dtw_dba_update included) and dsp_hmm_* and dsp_vq_* and dsp_dhmm_* (dsp_dhmm_decode, dsp_dhmm_forward and dsp_dhmm_expect included) and dsp_pitch_* and dsp_lpc_* entry points: new symbols only, no
                               existing signature or meaning changed, so callers built against 6 keep
                               working (a binding that needs them checks for the symbols) */
 
@@ -712,6 +712,84 @@ int dsp_dhmm_accumulate(const int32_t *n_states, int64_t C, int Smax, int K, con
                         int64_t N, int T, const int32_t *group_start, const int32_t *members, int64_t P,
                         const int32_t *seg, const double *score, int32_t *cnt_emit, int32_t *cnt, int32_t *n_valid,
                         double *total, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Forward scoring (evaluation) and forward-backward expected counts (Baum-Welch training) of the
+ * discrete-observation HMMs above, in the SCALED PROBABILITY domain.  csrc/dhmm_fb.hip, DESIGN.md §4.16.
+ * Every row of the trellis is rescaled by a power of two taken from the row's own maximum, so the device
+ * needs only fp64 multiply, add, max, frexp and ldexp and one IEEE division per frame.  Every output is
+ * defined bit for bit; the device takes no logarithm: the likelihood leaves it as a (mantissa, exponent)
+ * pair and the caller takes the one log.
+ *
+ * Symbols: sym int32 [N, T] with len int32 [N], 1 <= T <= 1024, as in dsp_dhmm_score.  Alphabet: K <= 256.
+ * Probability model set: C <= 2^20 models padded to Smax <= 32 states: pemit float64 [C, Smax, K], pstay,
+ *   padv float64 [C, Smax], n_states int32 [C].  Every entry read is either 0.0 or lies in [2^-300, 1],
+ *   never NaN; padv[c, S-1] and the rows s >= S are never read.
+ * Arithmetic: every operation is rounded to fp64, products are formed as written, nothing is fused, fp64
+ *   denormals are kept.  Below B = pemit, a = pstay, d = padv, o = the symbol row.
+ * Forward, for a model of S states and a sequence of n frames:
+ *     u_0(0) = B[0,o_0];   u_0(s>0) = 0
+ *     u_t(s) = (A_{t-1}(s)*a[s] + A_{t-1}(s-1)*d[s-1]) * B[s,o_t]   (the second product is 0.0 at s = 0)
+ *     m_t = max_s u_t(s)
+ *       m_t > 0:  k_t = frexp exponent of m_t  (m_t = f * 2^k_t, 0.5 <= f < 1)
+ *                 A_t(s) = ldexp(u_t(s), -k_t);   E_t = E_{t-1} + k_t     (E_{-1} = 0)
+ *       m_t == 0: A_t = u_t (all zeros);  E_t = E_{t-1}
+ *     result:  v = A_{n-1}(S-1)
+ *       v == 0:  (mant, expo) = (0.0, 0), "zero likelihood"
+ *       else:    (f, k) = frexp(v);  mant = f in [0.5, 1);  expo = E_{n-1} + k     (int32)
+ *   The likelihood of ending in the last state is mant * 2^expo.  It is zero when n < S (this comes out of
+ *   the recurrence), when n < 1 or n > T, when n_states[c] is outside 1 .. Smax, for a list entry outside
+ *   [0, N), and when any sym[t], t < n, lies outside [0, K) (such a symbol never indexes the table).
+ *   Label: the model with the largest likelihood, decided exactly: the larger expo wins, then the larger
+ *   mant, ties go to the smaller index; -1 when every model's likelihood is zero.
+ * Backward:
+ *     Bh_{n-1}(S-1) = 1;   Bh_{n-1}(s < S-1) = 0
+ *     w_t(s) = a[s]*(B[s,o_{t+1}]*Bh_{t+1}(s)) + d[s]*(B[s+1,o_{t+1}]*Bh_{t+1}(s+1))   (second term 0.0 at s = S-1)
+ *   Each row is rescaled by its own maximum's exponent exactly as above; a zero row stays zero.  No exponent
+ *   is kept: the per-frame normalisation below cancels it.
+ * Posteriors:
+ *     g_t(s) = A_t(s) * Bh_t(s)
+ *     D_t    = g_t(0) + g_t(1) + ... + g_t(S-1)    (ascending s)
+ *     r_t    = 1.0 / D_t                           (one IEEE division per frame)
+ *     gamma_t(s) = g_t(s) * r_t
+ *   A member is valid when its index and length are valid, all its symbols at t < n lie in [0, K), its
+ *   model's n_states is valid and every D_t, 0 <= t < n, is > 0 (D_{n-1} > 0 is the forward result being
+ *   non-zero) and has a finite reciprocal r_t: a positive D_t below about 2^-1024 (a subnormal) gives
+ *   r_t = +inf and makes the member invalid like D_t == 0, so no +inf and no 0 x inf is ever formed and
+ *   gamma, occ_emit and n_valid hold finite values only.  Any other member is skipped whole.
+ * Expected counts, for a valid pair p of model c:
+ *     G_p[s,k]        the sum of gamma_t(s) over the frames with o_t = k, added in DESCENDING t from 0.0
+ *     occ_emit[c,s,k] the G_p[s,k] of the valid members added in list order, starting from 0.0
+ *     n_valid[c]      the valid members
+ *   Rows s >= S are zeros; models without a valid member are zeros.  No transition counts are needed: in a
+ *   left-to-right model without skips every path leaves each state s < S-1 exactly once, so the expected
+ *   advance count of a state is n_valid and the expected stay count is its occupancy minus n_valid.
+ *
+ * dsp_dhmm_forward: every sequence against every model: mant float64 [N, C], expo int32 [N, C], label
+ *   int32 [N].  Each may be NULL (a label without mant or expo keeps them in the workspace).
+ * dsp_dhmm_expect: over dsp_dhmm_align's CSR pair list: mant float64 [P], expo int32 [P] and gamma float64
+ *   [P, T, Smax], each of which may be NULL, and occ_emit float64 [C, Smax, K], n_valid int32 [C].  gamma is
+ *   written at t < n and s < S for valid members; every other entry of gamma is 0.0.  mant and expo are
+ *   written for the pairs inside a group (group_start[0] <= p < group_start[C]); entries of pairs outside
+ *   every group are left as the caller had them.
+ * workspace  device scratch of dsp_dhmm_fb_workspace_bytes(C, N, P, T, Smax, K) bytes (0: sizes outside the
+ *   plan; P = 0 for dsp_dhmm_forward): the model set repacked, the scaled forward rows of each resident wave
+ *   (at most 256 MiB; this caps the waves), one table G_p per pair of a pair chunk (at most 256 MiB; the
+ *   list is processed in such chunks), one int32 per pair, and N x C (mant, expo) for labels without them.
+ *   Nothing in it is carried from one call to the next.
+ * Both check their host arguments before any launch (DSP_ERR_ARGS, DSP_ERR_WORKSPACE), return DSP_OK with
+ * nothing to do, make no host synchronisation and no allocation, and write only to their outputs and the
+ * workspace, on the caller's stream.
+ */
+size_t dsp_dhmm_fb_workspace_bytes(int64_t C, int64_t N, int64_t P, int T, int Smax, int K);
+int dsp_dhmm_forward(const double *pemit, const double *pstay, const double *padv, const int32_t *n_states, int64_t C,
+                     int Smax, int K, const int32_t *sym, const int32_t *len, int64_t N, int T, double *mant,
+                     int32_t *expo, int32_t *label, void *workspace, size_t workspace_bytes, void *stream);
+int dsp_dhmm_expect(const double *pemit, const double *pstay, const double *padv, const int32_t *n_states, int64_t C,
+                    int Smax, int K, const int32_t *sym, const int32_t *len, int64_t N, int T,
+                    const int32_t *group_start, const int32_t *members, int64_t P, double *mant, int32_t *expo,
+                    double *gamma, double *occ_emit, int32_t *n_valid, void *workspace, size_t workspace_bytes,
+                    void *stream);
 
 /*
  * Connected-word decoding: the one-pass (token-passing) Viterbi over a loop of the word models of a
