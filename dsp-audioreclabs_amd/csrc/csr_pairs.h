@@ -2,7 +2,9 @@
 // vq.hip (nearest codewords, Lloyd re-estimation) do with a CSR pair list (group_start [groups + 1], members [P]: group c against the sequences
 // members[p], p in [group_start[c], group_start[c+1])):
 //   csr_walk         the tiles of a launch's groups dealt to its persistent waves, a lane per pair
-//   csr_zero_counts, csr_grid   the host side of the chunked re-estimations
+//   csr_group_of     the group that holds a pair
+//   csr_waves        the persistent waves of a launch
+//   csr_zero, csr_grid   the host side of the chunked re-estimations
 //   csr_label        the label of a score matrix [N, C] (hmm.hip, vq.hip)
 #pragma once
 #include <algorithm>
@@ -57,16 +59,30 @@ __device__ __forceinline__ void csr_walk(int G, int wv, int nc, const int32_t *_
     }
 }
 
-// a [na] = 0 and b [nb] = 0 before the first pair chunk of a re-estimation.  A kernel, not a memset: the
-// call stays a chain of kernel launches, which is what a captured single-stream graph of it replays in order.
-static __global__ __launch_bounds__(256) void csr_zero_counts(int32_t *__restrict__ a, int64_t na,
-                                                              int32_t *__restrict__ b, int64_t nb)
+// the group that holds pair p: the last c of 0 .. C-1 with group_start[c] <= p (0 when there is none)
+__device__ __forceinline__ int64_t csr_group_of(const int32_t *__restrict__ group_start, int64_t C, int64_t p)
+{
+    int64_t lo = 0, hi = C;
+    while (hi - lo > 1) {
+        const int64_t mid = (lo + hi) / 2;
+        if (group_start[mid] <= p)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
+// a [na] and b [nb] to zeros before the first pair chunk of a re-estimation.  A kernel, not a memset: the call
+// stays a chain of kernel launches, which is what a captured single-stream graph of it replays in order.
+template <class A, class B>
+static __global__ __launch_bounds__(256) void csr_zero(A *__restrict__ a, int64_t na, B *__restrict__ b, int64_t nb)
 {
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < na + nb; e += (int64_t)gridDim.x * 256) {
         if (e < na)
-            a[e] = 0;
+            a[e] = A(0);
         else
-            b[e - na] = 0;
+            b[e - na] = B(0);
     }
 }
 
@@ -87,6 +103,15 @@ static __global__ __launch_bounds__(256) void csr_label(const double *__restrict
         }
         label[r] = arg;
     }
+}
+
+// The persistent waves of a launch of tiles tiles: at most DTW_WAVES, and where every wave owns bytes_per_wave
+// bytes of the workspace (0: none) no more than CSR_WAVE_CAP holds
+static constexpr size_t CSR_WAVE_CAP = 256u << 20;
+static inline int csr_waves(int64_t tiles, size_t bytes_per_wave)
+{
+    const int64_t cap = bytes_per_wave ? std::max<int64_t>(1, (int64_t)(CSR_WAVE_CAP / bytes_per_wave)) : DTW_WAVES;
+    return (int)std::max<int64_t>(1, std::min<int64_t>(tiles, std::min<int64_t>(DTW_WAVES, cap)));
 }
 
 // blocks of 256 threads striding over elems elements

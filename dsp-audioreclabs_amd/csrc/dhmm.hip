@@ -19,7 +19,7 @@
 // The score is +inf when n < S (it comes out of the recurrence), when n < 1 or n > T, when n_states is
 // outside 1 .. Smax, for a list entry outside [0, N), and when any sym[t], t < n, lies outside [0, K):
 // such a symbol never indexes the table (the index is clamped and the result forced).
-// Path.  hmm.hip's, word for word: walk back from (n-1, S-1), the predecessor is the advance iff b < a
+// Path.  hmm.hip's (hmm_internal.h's hmm_walk_back): walk back from (n-1, S-1), the predecessor is the advance iff b < a
 // strictly; seg int32 [P, Smax], seg[s] the first frame of state s, -1 behind the model's states and
 // everywhere for a pair whose score is +inf.
 // Re-estimation from a GIVEN seg [P, Smax] and score [P]: a member is valid when its index and length
@@ -30,75 +30,31 @@
 // Rows s >= S are zeros; a model without a valid member or with an invalid n_states has all-zero counts,
 // total 0.0 and n_valid 0.  The counts are integers, so the order the device adds them in is free.
 //
-// Kernels:
-//   dhmm_pack   the set as one record per model in the workspace, END-aligned to NS register slots
-//              (NS = 8, 16 or 32, the smallest that holds Smax): state s of a model of S states sits in
-//              slot s + NS - S, so the result is always slot NS - 1; the leading slots hold zeros (their
-//              cells start at +inf and stay there).  A record is the emission table transposed to
-//              [K][NS] -- one symbol's slots contiguous -- and then (stay, adv[s-1]) per slot.
+// Kernels (the record, its staging and the seg rows are hmm_internal.h's):
 //   dhmm_dp<NS, DIR>  hmm_dp's shape: one persistent wave per tile of ONE model and 64 sequences, a lane
-//              per sequence, the tiles from csr_pairs.h's csr_walk; the NS cells of a lane in registers,
-//              the state loop fully unrolled, slots swept in descending order in place; the lane's
-//              symbol one row ahead through the vector path.  The record is staged into LDS when the
-//              tile's model is not the one staged last: symbol k's slots at byte k * (8 NS + 16), the
-//              16 bytes of padding making the pitch an odd number of 16-byte units, so symbols k and k'
-//              share a bank window only when k = k' (mod 16) -- and then broadcast if k = k'.  A row
-//              is NS / 2 ds_read_b128 of the lane's own symbol's slots (a true gather, two states per
-//              read) and NS broadcast ds_read_b128 of (stay, adv[s-1]); no scalar load in the loop,
-//              so the waits are counted lgkmcnt.  4 fp64 instructions per cell; DIR as hmm_dp's.
+//              per sequence, the tiles from csr_pairs.h's csr_walk; the NS cells of a lane in registers
+//              (NS = 8, 16 or 32 slots, the smallest that holds Smax), the state loop fully unrolled, slots
+//              swept in descending order in place; the lane's symbol one row ahead through the vector path.
+//              The record is staged into LDS when the tile's model is not the one staged last.  A row is
+//              NS / 2 ds_read_b128 of the lane's own symbol's slots (a true gather, two states per read) and
+//              NS broadcast ds_read_b128 of (stay, adv[s-1]); no scalar load in the loop, so the waits are
+//              counted lgkmcnt.  4 fp64 instructions per cell; DIR as hmm_dp's.
 //   csr_label  (csr_pairs.h) the label of a score matrix.
-//   dhmm_pairs / dhmm_count / dhmm_totals   the re-estimation: a thread per pair (its model by bisection
-//              of group_start, the seg row and symbol range checks), a thread per (pair, frame) (the
-//              frame's state from the seg row, vector atomic adds on the int32 counts), a thread per
-//              model (the ordered total and n_valid); csr_zero_counts zeroes the counts first.
+//   dhmm_pairs / dhmm_count / dhmm_totals   the re-estimation: a thread per pair (its model, the seg row
+//              and symbol range checks), a thread per (pair, frame) (the frame's state from the seg row,
+//              vector atomic adds on the int32 counts), a thread per model (the ordered total and n_valid);
+//              csr_zero zeroes the counts first.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <algorithm>
 
 #include "csr_pairs.h"
-#include "dhmm_internal.h"
 #include "dsp_audiorec.h"
 #include "dtw_internal.h"
+#include "hmm_internal.h"
 
 namespace dsp {
-
-static constexpr int64_t DHMM_CMAX = 1 << 20;        // models in a set at most
-static constexpr int DHMM_GCHUNK = 1024;             // models per launch at most
-static constexpr size_t DHMM_WAVE_CAP = 256u << 20;  // bytes of direction words per launch
-static constexpr int DHMM_BATCH = 16;                // members whose loads a totals thread keeps in flight
-
-// doubles of one model's record: [K][NS] emissions, then [NS][2] (stay, adv[s-1])
-static inline size_t dhmm_record(int K, int NS) { return (size_t)K * NS + 2 * (size_t)NS; }
-// bytes between two symbols' slots in LDS: an odd number of 16-byte units (NS is a multiple of 4)
-__host__ __device__ static inline int dhmm_pitch(int NS) { return NS * 8 + 16; }
-static inline size_t dhmm_lds_bytes(int K, int NS) { return (size_t)K * dhmm_pitch(NS) + (size_t)NS * 16; }
-
-// rec [C][K * NS + 2 NS], see above; a model with an invalid n_states gets zeros (never read)
-__global__ __launch_bounds__(256) void dhmm_pack(const double *__restrict__ emit, const double *__restrict__ stay,
-                                                 const double *__restrict__ adv, const int32_t *__restrict__ n_states,
-                                                 int64_t C, int Smax, int K, int NS, double *__restrict__ rec)
-{
-    const int64_t R = (int64_t)K * NS + 2 * NS, total = C * R;
-    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
-        const int64_t c = e / R;
-        const int r = (int)(e % R);
-        const bool tab = r < K * NS;
-        const int j = tab ? r % NS : (r - K * NS) / 2;
-        const int S = n_states[c], s = j - (NS - S);
-        double v = 0.0;
-        if (S >= 1 && S <= Smax && s >= 0) {
-            const int64_t cs = c * Smax + s;
-            if (tab)
-                v = emit[cs * K + r / NS];
-            else if ((r - K * NS) % 2 == 0)
-                v = stay[cs];
-            else
-                v = s > 0 ? adv[cs - 1] : 0.0;
-        }
-        rec[e] = v;
-    }
-}
 
 #pragma clang fp contract(off)
 // One row of the NS slots: v holds row t-1 and is replaced by row t; erow: the slots of the lane's own
@@ -139,10 +95,9 @@ template <int NS, bool DIR>
 __device__ __forceinline__ double dhmm_sweep(const unsigned char *tab, const double2 *tr, int j0, int K,
                                              const int32_t *__restrict__ sr, int n, int nmax, uint32_t *dir)
 {
-    constexpr int PITCH = NS * 8 + 16;
     double v[NS];
     uint32_t word = 0;
-    auto row_of = [&](int k) { return (const double2 *)(tab + (unsigned)min((unsigned)k, (unsigned)(K - 1)) * PITCH); };
+    auto row_of = [&](int k) { return (const double2 *)(tab + (unsigned)min((unsigned)k, (unsigned)(K - 1)) * dhmm_pitch(NS)); };
     int k = sr[0];
     bool bad = n >= 1 && (unsigned)k >= (unsigned)K;
     dhmm_row<NS, true, DIR>(v, row_of(k), tr, j0, word);
@@ -164,7 +119,7 @@ __device__ __forceinline__ double dhmm_sweep(const unsigned char *tab, const dou
 // The models c = 0 .. nc-1 of this launch (rec, n_states and group_start already point at the first
 // one, model c0 of the set).  group_start == NULL: every model against all N sequences, the result
 // of (sequence r, model c) at score[r * C + c0 + c]; else the CSR pairs, outputs indexed by p.
-// Dynamic LDS: K * (8 NS + 16) + 16 NS bytes.  At 32 slots the LDS lets about two waves per SIMD stay
+// Dynamic LDS: dhmm_lds_bytes(K, NS).  At 32 slots the LDS lets about two waves per SIMD stay
 // resident anyway (K = 64: nine tables per CU), so the scheduler is told to plan for two: with the
 // registers that frees it keeps up to 14 transition reads in flight instead of one.
 template <int NS, bool DIR>
@@ -176,10 +131,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, NS == 32 
                                               int32_t *__restrict__ seg, uint32_t *dir_ws)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char dhmm_lds[];
-    constexpr int PITCH = NS * 8 + 16;
     const int lane = (int)threadIdx.x, wv = (int)blockIdx.x;
-    const size_t R = (size_t)K * NS + 2 * NS;
-    const double2 *tr = (const double2 *)(dhmm_lds + (size_t)K * PITCH);
+    const double2 *tr = (const double2 *)(dhmm_lds + dhmm_tr_offset(K, NS));
     uint32_t *dir = DIR && seg ? dir_ws + (size_t)wv * (size_t)T * 64 + lane : nullptr;
     int staged = -1;
     csr_walk((int)gridDim.x, wv, nc, group_start, 0, group_start ? P : (int)N, members, len, N, T,
@@ -190,42 +143,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, NS == 32 
                  double res = INFINITY;
                  if (sok && ln.lmax > 0) {
                      if (staged != cg) {
-                         // 16-byte pieces of the record: K * NS / 2 of the table, then NS of the transitions
-                         const double2 *__restrict__ src = (const double2 *)(rec + (size_t)cg * R);
-                         const int ne = K * (NS / 2);
-                         __syncthreads();  // one wave: the reads of the table staged before are done
-                         for (int i = lane; i < ne + NS; i += 64) {
-                             const int kk = i / (NS / 2), jj = i % (NS / 2);
-                             const size_t at = i < ne ? (size_t)kk * PITCH + (size_t)jj * 16
-                                                      : (size_t)K * PITCH + (size_t)(i - ne) * 16;
-                             *(double2 *)(dhmm_lds + at) = src[i];
-                         }
-                         __syncthreads();
+                         dhmm_stage<NS>(dhmm_lds, rec + (size_t)cg * dhmm_record(K, NS), K, lane);
                          staged = cg;
                      }
                      res = dhmm_sweep<NS, DIR>(dhmm_lds, tr, NS - S, K, sym + (int64_t)ln.row * T, n, ln.lmax, dir);
                  }
                  if (!ln.inr) return;
                  if (score) score[group_start ? p : p * C + c0 + cg] = res;
-                 if (!DIR || !seg) return;
-                 int32_t *__restrict__ ps = seg + p * Smax;
-                 int filled = 0;
-                 if (res < INFINITY) {
-                     // the lane's own walk back: state s is slot s + NS - S, that bit of a row's word
-                     int s = S - 1;
-                     for (int r = n - 1; r >= 1 && s > 0; r--)
-                         if ((dir[(size_t)r * 64] >> (s + NS - S)) & 1) ps[s--] = r;
-                     for (; s > 0; s--) ps[s] = s;  // not reached with the sweep's own words
-                     ps[0] = 0;
-                     filled = S;
-                 }
-                 for (int i = filled; i < Smax; i++) ps[i] = -1;
+                 if (DIR && seg) hmm_walk_back(dir, n, S, NS, Smax, res < INFINITY, seg + p * Smax);
              });
 }
 
 // ---- re-estimation ----
-// A thread per pair: pmodel[p] = its model (the group that holds p, by bisection of group_start) when
-// the member is valid, else -1.
+// A thread per pair: pmodel[p] = its model (the group that holds p) when the member is valid, else -1.
 __global__ __launch_bounds__(256) void dhmm_pairs(const int32_t *__restrict__ n_states, int64_t C, int Smax, int K,
                                                   const int32_t *__restrict__ sym, const int32_t *__restrict__ len,
                                                   int64_t N, int T, const int32_t *__restrict__ group_start,
@@ -233,23 +163,12 @@ __global__ __launch_bounds__(256) void dhmm_pairs(const int32_t *__restrict__ n_
                                                   const int32_t *__restrict__ seg, int32_t *__restrict__ pmodel)
 {
     for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < P; p += (int64_t)gridDim.x * 256) {
-        int64_t lo = 0, hi = C;  // the last c with group_start[c] <= p
-        while (hi - lo > 1) {
-            const int64_t mid = (lo + hi) / 2;
-            if (group_start[mid] <= p)
-                lo = mid;
-            else
-                hi = mid;
-        }
+        const int64_t lo = csr_group_of(group_start, C, p);
         const int S = n_states[lo], mem = members[p];
         const int32_t *__restrict__ ps = seg + p * Smax;
         bool ok = S >= 1 && S <= Smax && mem >= 0 && mem < N && p >= group_start[lo] && p < group_start[lo + 1];
         const int n = ok ? len[mem] : 0;
-        ok = ok && n >= 1 && n <= T && ps[0] == 0;
-        for (int s = 0; ok && s < S; s++) {
-            const int b = ps[s], e = s + 1 < S ? ps[s + 1] : n;
-            ok = b >= 0 && b < e && e <= n;
-        }
+        ok = ok && n >= 1 && n <= T && hmm_seg_ok(ps, S, n);
         if (ok) {
             const int32_t *__restrict__ sr = sym + (int64_t)mem * T;
             unsigned worst = 0;
@@ -295,17 +214,17 @@ __global__ __launch_bounds__(256) void dhmm_totals(int64_t C, const int32_t *__r
         const int g0 = clampi(group_start[c], 0, (int)P), g1 = clampi(group_start[c + 1], 0, (int)P);
         int nv = 0;
         double tot = 0.0;
-        for (int p0 = g0; p0 < g1; p0 += DHMM_BATCH) {
-            bool ok[DHMM_BATCH];
-            double sc[DHMM_BATCH];
+        for (int p0 = g0; p0 < g1; p0 += HMM_BATCH) {
+            bool ok[HMM_BATCH];
+            double sc[HMM_BATCH];
 #pragma unroll
-            for (int u = 0; u < DHMM_BATCH; u++) {
+            for (int u = 0; u < HMM_BATCH; u++) {
                 const bool in_group = p0 + u < g1;
                 ok[u] = in_group && pmodel[p0 + u] == c;
                 sc[u] = in_group ? score[p0 + u] : 0.0;
             }
 #pragma unroll
-            for (int u = 0; u < DHMM_BATCH; u++) {
+            for (int u = 0; u < HMM_BATCH; u++) {
                 if (!ok[u]) continue;
                 tot = nv == 0 ? sc[u] : tot + sc[u];
                 nv++;
@@ -318,12 +237,6 @@ __global__ __launch_bounds__(256) void dhmm_totals(int64_t C, const int32_t *__r
 #pragma clang fp contract(on)
 
 // ---- host side ----
-static bool dhmm_in_plan(int64_t C, int64_t N, int64_t P, int T, int Smax, int K)
-{
-    return C >= 0 && C <= DHMM_CMAX && N >= 0 && N < 0x7fffffff && P >= 0 && P < 0x7fffffff && Smax >= 1 &&
-           Smax <= DHMM_SMAX && K >= 1 && K <= DHMM_KMAX && T >= 1 && T <= DTW_TMAX;
-}
-
 // workspace: [records of the C models][direction words of G waves][score [N, C], for labels without
 // scores][the pairs' models: dsp_dhmm_accumulate]
 struct DhmmPlan {
@@ -331,40 +244,19 @@ struct DhmmPlan {
     size_t rec, dir, score, pmodel;
     size_t total() const { return rec + dir + score + pmodel; }
 };
-static int dhmm_waves(int64_t tiles, int T, bool with_dir)
-{
-    const int64_t cap = with_dir ? std::max<int64_t>(1, (int64_t)(DHMM_WAVE_CAP / ((size_t)T * 64 * 4))) : DTW_WAVES;
-    return (int)std::max<int64_t>(1, std::min<int64_t>(tiles, std::min<int64_t>(DTW_WAVES, cap)));
-}
 static DhmmPlan dhmm_plan(int64_t C, int64_t N, int64_t P, int T, int Smax, int K)
 {
     DhmmPlan pl;
     pl.NS = dhmm_slots(Smax);
-    pl.G = dhmm_waves(P / 64 + std::min<int64_t>(C, DHMM_GCHUNK), T, true);
+    pl.G = csr_waves(P / 64 + std::min<int64_t>(C, HMM_GCHUNK), hmm_dir_bytes(T));
     pl.rec = up256((size_t)C * dhmm_record(K, pl.NS) * 8);
-    pl.dir = up256((size_t)pl.G * T * 64 * 4);
+    pl.dir = up256(pl.G * hmm_dir_bytes(T));
     pl.score = up256((size_t)N * C * 8);
     pl.pmodel = up256((size_t)P * 4);
     return pl;
 }
 
-template <int NS, bool DIR>
-static hipError_t dhmm_launch(dim3 grid, size_t lds, hipStream_t s, const double *rec, const int32_t *n_states, int c0,
-                              int nc, int64_t C, int Smax, int K, const int32_t *sym, const int32_t *len, int64_t N, int T,
-                              const int32_t *group_start, const int32_t *members, int P, double *score, int32_t *seg,
-                              uint32_t *dir)
-{
-    if (lds > 65536) {  // K = 256 at 32 slots: past the default limit of dynamic LDS
-        const hipError_t e = hipFuncSetAttribute((const void *)dhmm_dp<NS, DIR>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL((dhmm_dp<NS, DIR>), grid, dim3(64), lds, s, rec, n_states, c0, nc, C, Smax, K, sym, len, N, T,
-                       group_start, members, P, score, seg, dir);
-    return hipSuccess;
-}
-
-// the records, then the DP over all models in launches of at most DHMM_GCHUNK
+// the records, then the DP over all models in launches of at most HMM_GCHUNK
 template <bool DIR>
 static int dhmm_run(hipStream_t s, const DhmmPlan &pl, void *ws, const double *emit, const double *stay, const double *adv,
                     const int32_t *n_states, int64_t C, int Smax, int K, const int32_t *sym, const int32_t *len, int64_t N,
@@ -375,22 +267,20 @@ static int dhmm_run(hipStream_t s, const DhmmPlan &pl, void *ws, const double *e
     const int NS = pl.NS;
     const size_t R = dhmm_record(K, NS), lds = dhmm_lds_bytes(K, NS);
     hipLaunchKernelGGL(dhmm_pack, csr_grid(C * (int64_t)R), dim3(256), 0, s, emit, stay, adv, n_states, C, Smax, K, NS, rec);
-    for (int64_t c0 = 0; c0 < C; c0 += DHMM_GCHUNK) {
-        const int64_t nc = std::min<int64_t>(DHMM_GCHUNK, C - c0);
+    for (int64_t c0 = 0; c0 < C; c0 += HMM_GCHUNK) {
+        const int64_t nc = std::min<int64_t>(HMM_GCHUNK, C - c0);
         const int64_t tiles = group_start ? P / 64 + nc : nc * ((N + 63) / 64);
-        const int G = DIR ? std::min(pl.G, dhmm_waves(tiles, T, true)) : dhmm_waves(tiles, T, false);
+        const int G = DIR ? std::min(pl.G, csr_waves(tiles, hmm_dir_bytes(T))) : csr_waves(tiles, 0);
         const double *rc = rec + (size_t)c0 * R;
         const int32_t *gs = group_start ? group_start + c0 : nullptr;
-        hipError_t e;
-        if (NS == 8)
-            e = dhmm_launch<8, DIR>(dim3((unsigned)G), lds, s, rc, n_states + c0, (int)c0, (int)nc, C, Smax, K, sym, len, N, T,
-                                    gs, members, (int)P, score, seg, dir);
-        else if (NS == 16)
-            e = dhmm_launch<16, DIR>(dim3((unsigned)G), lds, s, rc, n_states + c0, (int)c0, (int)nc, C, Smax, K, sym, len, N, T,
-                                     gs, members, (int)P, score, seg, dir);
-        else
-            e = dhmm_launch<32, DIR>(dim3((unsigned)G), lds, s, rc, n_states + c0, (int)c0, (int)nc, C, Smax, K, sym, len, N, T,
-                                     gs, members, (int)P, score, seg, dir);
+        const hipError_t e = dhmm_with_slots(NS, [&](auto ns) {
+            constexpr int SLOTS = decltype(ns)::value;
+            const hipError_t err = dhmm_lds_limit(dhmm_dp<SLOTS, DIR>, lds);
+            if (err == hipSuccess)
+                hipLaunchKernelGGL((dhmm_dp<SLOTS, DIR>), dim3((unsigned)G), dim3(64), lds, s, rc, n_states + c0, (int)c0, (int)nc,
+                                   C, Smax, K, sym, len, N, T, gs, members, (int)P, score, seg, dir);
+            return err;
+        });
         if (e != hipSuccess) return DSP_ERR_HIP + (int)e;
     }
     return dtw_launch_status();
@@ -456,7 +346,7 @@ extern "C" int dsp_dhmm_accumulate(const int32_t *n_states, int64_t C, int Smax,
     hipStream_t s = (hipStream_t)stream;
     int32_t *pmodel = (int32_t *)((char *)workspace + pl.rec + pl.dir + pl.score);
     const dim3 block(256);
-    hipLaunchKernelGGL(dsp::csr_zero_counts, dsp::csr_grid(C * Smax * (int64_t)(K + 1)), block, 0, s, cnt_emit,
+    hipLaunchKernelGGL((dsp::csr_zero<int32_t, int32_t>), dsp::csr_grid(C * Smax * (int64_t)(K + 1)), block, 0, s, cnt_emit,
                        C * Smax * (int64_t)K, cnt, C * (int64_t)Smax);
     if (P > 0) {
         hipLaunchKernelGGL(dsp::dhmm_pairs, dsp::csr_grid(P), block, 0, s, n_states, C, Smax, K, sym, len, N, T, group_start,

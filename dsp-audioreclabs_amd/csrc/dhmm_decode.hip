@@ -54,9 +54,9 @@
 
 #include <algorithm>
 
-#include "dhmm_internal.h"
 #include "dsp_audiorec.h"
 #include "dtw_internal.h"
+#include "hmm_internal.h"
 
 namespace dsp {
 
@@ -298,15 +298,6 @@ __global__ __launch_bounds__(64) void dhmm_decode(const double *__restrict__ tab
     }
 }
 
-template <int NS>
-static void decode_launch(int G, size_t lds, hipStream_t s, const double *tab, const double2 *tr, const int32_t *j0, int K,
-                                const int32_t *sym, const int32_t *len, int N, int T, int max_words, double *score,
-                                int32_t *n_words, int32_t *words, int32_t *start, double *cum)
-{
-    hipLaunchKernelGGL(dhmm_decode<NS>, dim3((unsigned)G), dim3(64), lds, s, tab, tr, j0, K, sym, len, N, T, max_words, score,
-                       n_words, words, start, cum);
-}
-
 }  // namespace dsp
 
 extern "C" size_t dsp_dhmm_decode_workspace_bytes(int64_t C, int64_t N, int T, int Smax, int K)
@@ -335,11 +326,9 @@ extern "C" int dsp_dhmm_decode(const double *emit, const double *stay, const dou
                        stay, adv, n_states, enter, (int)C, Smax, K, NS, tab, tr, j0);
     const int G = (int)std::min<int64_t>(N, dsp::DHMM_DECODE_WAVES);
     const size_t lds = dsp::decode_lds_bytes(T, NS);
-    if (NS == 8)
-        dsp::decode_launch<8>(G, lds, s, tab, tr, j0, K, sym, len, (int)N, T, max_words, score, n_words, words, start, cum);
-    else if (NS == 16)
-        dsp::decode_launch<16>(G, lds, s, tab, tr, j0, K, sym, len, (int)N, T, max_words, score, n_words, words, start, cum);
-    else
-        dsp::decode_launch<32>(G, lds, s, tab, tr, j0, K, sym, len, (int)N, T, max_words, score, n_words, words, start, cum);
+    dsp::dhmm_with_slots(NS, [&](auto ns) {
+        hipLaunchKernelGGL(dsp::dhmm_decode<decltype(ns)::value>, dim3((unsigned)G), dim3(64), lds, s, tab, tr, j0, K, sym, len,
+                           (int)N, T, max_words, score, n_words, words, start, cum);
+    });
     return dsp::dtw_launch_status();
 }

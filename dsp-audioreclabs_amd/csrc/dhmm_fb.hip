@@ -41,14 +41,12 @@
 // occ_emit[c,s,k] = the G_p[s,k] of the valid members added in list order from 0.0; rows s >= S and models
 // without a valid member are zeros; n_valid[c] counts the valid members.
 //
-// Kernels (dhmm_dp's shape, dhmm.hip):
-//   dhmm_fb_pack  dhmm_pack's record: the table transposed to [K][NS], then (stay, adv[s-1]) per slot,
-//              END-aligned to NS = 8, 16 or 32 slots.  The padding slots hold zero probabilities: their
-//              cells are 0.0, which no maximum and no sum sees, so the bits do not depend on NS.
+// Kernels (dhmm_dp's shape, dhmm.hip; the record, its pack kernel and its staging are hmm_internal.h's -- the
+// padding slots hold 0.0, here zero probabilities: their cells are 0.0, which no maximum and no sum sees, so
+// the bits do not depend on NS):
 //   dhmm_fwd<NS>  one persistent wave per tile of ONE model and 64 sequences (csr_walk), a lane per
-//              sequence, the NS cells in registers, the record staged in LDS with dhmm_dp's odd pitch,
-//              the lane's symbol one row ahead.  A cell is 3 multiplies, 1 add, 1 max and 1 ldexp; a row
-//              adds one frexp exponent.  Nothing is kept per row.
+//              sequence, the NS cells in registers, the lane's symbol one row ahead.  A cell is 3 multiplies,
+//              1 add, 1 max and 1 ldexp; a row adds one frexp exponent.  Nothing is kept per row.
 //   dhmm_fb<NS>   the same forward sweep storing the A rows [row][slot][lane] in the wave's own area of the
 //              workspace (the slots in front of the model's states are wave-uniform zeros and are not
 //              stored), then the backward sweep with Bh in registers: it reads the A rows back, forms D_t,
@@ -56,7 +54,7 @@
 //              plain load, add, store: the lane owns its pair.  Descending t is the sweep's own order.
 //   dhmm_fb_sum   the list-order add: a thread per (model, symbol, slot), the loads of 16 members issued
 //              together, skipped pairs contributing nothing, the sums carried in occ_emit from one pair
-//              chunk to the next (the pairs are chunked so the G_p tables stay inside DFB_GP_CAP bytes).
+//              chunk to the next (the pairs are chunked so the G_p tables stay inside DHMM_GP_CAP bytes).
 //   dhmm_fb_label the exact comparison of the (mant, expo) pairs.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -64,58 +62,11 @@
 #include <algorithm>
 
 #include "csr_pairs.h"
-#include "dhmm_internal.h"
 #include "dsp_audiorec.h"
 #include "dtw_internal.h"
+#include "hmm_internal.h"
 
 namespace dsp {
-
-static constexpr int64_t DFB_CMAX = 1 << 20;        // models in a set at most
-static constexpr int DFB_GCHUNK = 1024;             // models per launch at most
-static constexpr size_t DFB_ROWS_CAP = 256u << 20;  // bytes of stored A rows per launch (caps the waves)
-static constexpr size_t DFB_GP_CAP = 256u << 20;    // bytes of per-pair tables G_p per pair chunk
-static constexpr int DFB_BATCH = 16;                // members whose loads a sum thread keeps in flight
-
-// doubles of one model's record: [K][NS] probabilities, then [NS][2] (stay, adv[s-1])
-static inline size_t dfb_record(int K, int NS) { return (size_t)K * NS + 2 * (size_t)NS; }
-static inline size_t dfb_lds_bytes(int K, int NS) { return (size_t)K * (NS * 8 + 16) + (size_t)NS * 16; }
-
-// rec [C][K * NS + 2 NS]; a model with an invalid n_states gets zeros (never read)
-__global__ __launch_bounds__(256) void dhmm_fb_pack(const double *__restrict__ emit, const double *__restrict__ stay,
-                                                    const double *__restrict__ adv, const int32_t *__restrict__ n_states,
-                                                    int64_t C, int Smax, int K, int NS, double *__restrict__ rec)
-{
-    const int64_t R = (int64_t)K * NS + 2 * NS, total = C * R;
-    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
-        const int64_t c = e / R;
-        const int r = (int)(e % R);
-        const bool tab = r < K * NS;
-        const int j = tab ? r % NS : (r - K * NS) / 2;
-        const int S = n_states[c], s = j - (NS - S);
-        double v = 0.0;
-        if (S >= 1 && S <= Smax && s >= 0) {
-            const int64_t cs = c * Smax + s;
-            if (tab)
-                v = emit[cs * K + r / NS];
-            else if ((r - K * NS) % 2 == 0)
-                v = stay[cs];
-            else
-                v = s > 0 ? adv[cs - 1] : 0.0;
-        }
-        rec[e] = v;
-    }
-}
-
-// a [na] = 0.0 and b [nb] = 0: a kernel, not a memset, so a call stays a chain of kernel launches
-__global__ __launch_bounds__(256) void dhmm_fb_zero(double *__restrict__ a, int64_t na, int32_t *__restrict__ b, int64_t nb)
-{
-    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < na + nb; e += (int64_t)gridDim.x * 256) {
-        if (e < na)
-            a[e] = 0.0;
-        else
-            b[e - na] = 0;
-    }
-}
 
 // max of two values that are never NaN, as the one instruction it is (dtw_min's reason)
 __device__ __forceinline__ double dfb_max(double x, double y)
@@ -170,9 +121,8 @@ __device__ __forceinline__ void dfb_forward(const unsigned char *tab, const doub
                                             const int32_t *__restrict__ sr, int n, int nmax, double *rows, double &mant,
                                             int &expo)
 {
-    constexpr int PITCH = NS * 8 + 16;
     double v[NS];
-    auto row_of = [&](int k) { return (const double2 *)(tab + (unsigned)min((unsigned)k, (unsigned)(K - 1)) * PITCH); };
+    auto row_of = [&](int k) { return (const double2 *)(tab + (unsigned)min((unsigned)k, (unsigned)(K - 1)) * dhmm_pitch(NS)); };
     auto keep = [&](int t) {
 #pragma unroll
         for (int j = 0; j < NS; j++)
@@ -211,7 +161,6 @@ __device__ __forceinline__ bool dfb_backward(const unsigned char *tab, const dou
                                              const int32_t *__restrict__ sr, int n, int nmax, const double *rows, bool ok,
                                              double *__restrict__ gp, double *__restrict__ gam)
 {
-    constexpr int PITCH = NS * 8 + 16;
     double bh[NS];
 #pragma unroll
     for (int j = 0; j < NS; j++) bh[j] = 0.0;
@@ -223,7 +172,7 @@ __device__ __forceinline__ bool dfb_backward(const unsigned char *tab, const dou
 #pragma unroll
         for (int j = 0; j < NS; j++) a[j] = j >= j0 ? rows[((size_t)t * NS + j) * 64] : 0.0;
         // w_t from Bh_{t+1}: all zeros while t >= n - 1 (a zero row stays zero), so Bh_{n-1} is set below
-        const double2 *erow = (const double2 *)(tab + (unsigned)min((unsigned)kup, (unsigned)(K - 1)) * PITCH);
+        const double2 *erow = (const double2 *)(tab + (unsigned)min((unsigned)kup, (unsigned)(K - 1)) * dhmm_pitch(NS));
 #pragma unroll
         for (int i = 0; i < NS / 2; i++) {
             const double2 e = erow[i];
@@ -267,25 +216,9 @@ __device__ __forceinline__ bool dfb_backward(const unsigned char *tab, const dou
 }
 #pragma clang fp contract(on)
 
-// the record of model cg into LDS: symbol k's slots at byte k * (8 NS + 16), then the transitions
-template <int NS>
-__device__ __forceinline__ void dfb_stage(unsigned char *lds, const double *__restrict__ rec, int K, int lane)
-{
-    constexpr int PITCH = NS * 8 + 16;
-    const double2 *__restrict__ src = (const double2 *)rec;
-    const int ne = K * (NS / 2);
-    __syncthreads();  // one wave: the reads of the table staged before are done
-    for (int i = lane; i < ne + NS; i += 64) {
-        const int kk = i / (NS / 2), jj = i % (NS / 2);
-        const size_t at = i < ne ? (size_t)kk * PITCH + (size_t)jj * 16 : (size_t)K * PITCH + (size_t)(i - ne) * 16;
-        *(double2 *)(lds + at) = src[i];
-    }
-    __syncthreads();
-}
-
 // Every model c = 0 .. nc-1 of this launch (rec and n_states already point at the first one, model c0 of the
 // set) against all N sequences: the result of (sequence r, model c) at [r * C + c0 + c].  Dynamic LDS:
-// K * (8 NS + 16) + 16 NS bytes.
+// dhmm_lds_bytes(K, NS).
 template <int NS>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, NS == 32 ? 2 : 8))) void dhmm_fwd(
     const double *__restrict__ rec, const int32_t *__restrict__ n_states, int c0, int nc, int64_t C, int Smax, int K,
@@ -294,8 +227,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, NS == 32 
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char dfb_lds[];
     const int lane = (int)threadIdx.x;
-    const size_t R = (size_t)K * NS + 2 * NS;
-    const double2 *tr = (const double2 *)(dfb_lds + (size_t)K * (NS * 8 + 16));
+    const double2 *tr = (const double2 *)(dfb_lds + dhmm_tr_offset(K, NS));
     int staged = -1;
     csr_walk((int)gridDim.x, (int)blockIdx.x, nc, nullptr, 0, (int)N, nullptr, len, N, T, [&](int cg, const CsrLane &ln) {
         const int S = n_states[cg];
@@ -303,7 +235,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, NS == 32 
         int e = 0;
         if (S >= 1 && S <= Smax && ln.lmax > 0) {
             if (staged != cg) {
-                dfb_stage<NS>(dfb_lds, rec + (size_t)cg * R, K, lane);
+                dhmm_stage<NS>(dfb_lds, rec + (size_t)cg * dhmm_record(K, NS), K, lane);
                 staged = cg;
             }
             dfb_forward<NS, false>(dfb_lds, tr, NS - S, K, sym + (int64_t)ln.row * T, ln.len, ln.lmax, nullptr, m, e);
@@ -328,8 +260,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, NS == 32 
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char dfb_lds[];
     const int lane = (int)threadIdx.x, wv = (int)blockIdx.x;
-    const size_t R = (size_t)K * NS + 2 * NS;
-    const double2 *tr = (const double2 *)(dfb_lds + (size_t)K * (NS * 8 + 16));
+    const double2 *tr = (const double2 *)(dfb_lds + dhmm_tr_offset(K, NS));
     double *rows = rows_ws + (size_t)wv * (size_t)T * NS * 64 + lane;
     int staged = -1;
     csr_walk((int)gridDim.x, wv, nc, group_start, p_lo, p_hi, members, len, N, T, [&](int cg, const CsrLane &ln) {
@@ -340,7 +271,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, NS == 32 
         bool valid = false;
         if (S >= 1 && S <= Smax && ln.lmax > 0) {
             if (staged != cg) {
-                dfb_stage<NS>(dfb_lds, rec + (size_t)cg * R, K, lane);
+                dhmm_stage<NS>(dfb_lds, rec + (size_t)cg * dhmm_record(K, NS), K, lane);
                 staged = cg;
             }
             const int32_t *__restrict__ sr = sym + (int64_t)ln.row * T;
@@ -378,17 +309,17 @@ __global__ __launch_bounds__(256) void dhmm_fb_sum(const int32_t *__restrict__ n
         double *__restrict__ out = occ_emit + ((size_t)c * Smax + s) * K + k;
         double acc = *out;
         int nv = 0;
-        for (int p0 = g0; p0 < g1; p0 += DFB_BATCH) {
-            bool ok[DFB_BATCH];
-            double g[DFB_BATCH];
+        for (int p0 = g0; p0 < g1; p0 += HMM_BATCH) {
+            bool ok[HMM_BATCH];
+            double g[HMM_BATCH];
 #pragma unroll
-            for (int u = 0; u < DFB_BATCH; u++) {
+            for (int u = 0; u < HMM_BATCH; u++) {
                 const bool in_group = p0 + u < g1;
                 ok[u] = in_group && pvalid[p0 + u] != 0;
                 g[u] = in_group ? gp[(size_t)(p0 + u - p_lo) * R + r] : 0.0;
             }
 #pragma unroll
-            for (int u = 0; u < DFB_BATCH; u++) {
+            for (int u = 0; u < HMM_BATCH; u++) {
                 if (!ok[u]) continue;
                 acc = acc + g[u];
                 nv++;
@@ -422,12 +353,6 @@ __global__ __launch_bounds__(256) void dhmm_fb_label(const double *__restrict__ 
 }
 
 // ---- host side ----
-static bool dfb_in_plan(int64_t C, int64_t N, int64_t P, int T, int Smax, int K)
-{
-    return C >= 0 && C <= DFB_CMAX && N >= 0 && N < 0x7fffffff && P >= 0 && P < 0x7fffffff && Smax >= 1 &&
-           Smax <= DHMM_SMAX && K >= 1 && K <= DHMM_KMAX && T >= 1 && T <= DTW_TMAX;
-}
-
 // workspace: [records of the C models][A rows of G waves][G_p tables of a chunk of PC pairs][a flag per
 // pair][mant [N, C] and expo [N, C], for labels without them]
 struct DfbPlan {
@@ -436,19 +361,16 @@ struct DfbPlan {
     size_t rec, rows, gp, pvalid, mant, expo;
     size_t total() const { return rec + rows + gp + pvalid + mant + expo; }
 };
-static int dfb_waves(int64_t tiles, int T, int NS, bool with_rows)
-{
-    const int64_t cap = with_rows ? std::max<int64_t>(1, (int64_t)(DFB_ROWS_CAP / ((size_t)T * NS * 512))) : DTW_WAVES;
-    return (int)std::max<int64_t>(1, std::min<int64_t>(tiles, std::min<int64_t>(DTW_WAVES, cap)));
-}
+// bytes of A rows a persistent wave owns in the workspace: [row][slot][lane] doubles
+static size_t dfb_rows_bytes(int T, int NS) { return (size_t)T * NS * 512; }
 static DfbPlan dfb_plan(int64_t C, int64_t N, int64_t P, int T, int Smax, int K)
 {
     DfbPlan pl;
     pl.NS = dhmm_slots(Smax);
-    pl.G = dfb_waves(P / 64 + std::min<int64_t>(C, DFB_GCHUNK), T, pl.NS, true);
-    pl.PC = std::min<int64_t>(P, std::max<int64_t>(64, (int64_t)(DFB_GP_CAP / ((size_t)K * pl.NS * 8))));
-    pl.rec = up256((size_t)C * dfb_record(K, pl.NS) * 8 + 8);  // never 0, which says "outside the plan"
-    pl.rows = P > 0 ? up256((size_t)pl.G * T * pl.NS * 512) : 0;
+    pl.G = csr_waves(P / 64 + std::min<int64_t>(C, HMM_GCHUNK), dfb_rows_bytes(T, pl.NS));
+    pl.PC = std::min<int64_t>(P, std::max<int64_t>(64, (int64_t)(DHMM_GP_CAP / ((size_t)K * pl.NS * 8))));
+    pl.rec = up256((size_t)C * dhmm_record(K, pl.NS) * 8 + 8);  // never 0, which says "outside the plan"
+    pl.rows = P > 0 ? up256(pl.G * dfb_rows_bytes(T, pl.NS)) : 0;
     pl.gp = up256((size_t)pl.PC * K * pl.NS * 8);
     pl.pvalid = up256((size_t)P * 4);
     pl.mant = up256((size_t)N * C * 8);
@@ -456,42 +378,11 @@ static DfbPlan dfb_plan(int64_t C, int64_t N, int64_t P, int T, int Smax, int K)
     return pl;
 }
 
-template <class Kernel>
-static hipError_t dfb_lds_limit(Kernel kernel, size_t lds)
-{
-    if (lds <= 65536) return hipSuccess;  // K = 256 at 32 slots: past the default limit of dynamic LDS
-    return hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-}
-
-template <int NS>
-static hipError_t dfb_launch_fwd(dim3 grid, size_t lds, hipStream_t s, const double *rec, const int32_t *n_states, int c0,
-                                 int nc, int64_t C, int Smax, int K, const int32_t *sym, const int32_t *len, int64_t N, int T,
-                                 double *mant, int32_t *expo)
-{
-    const hipError_t e = dfb_lds_limit(dhmm_fwd<NS>, lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(dhmm_fwd<NS>, grid, dim3(64), lds, s, rec, n_states, c0, nc, C, Smax, K, sym, len, N, T, mant, expo);
-    return hipSuccess;
-}
-
-template <int NS>
-static hipError_t dfb_launch_fb(dim3 grid, size_t lds, hipStream_t s, const double *rec, const int32_t *n_states, int nc,
-                                int Smax, int K, const int32_t *sym, const int32_t *len, int64_t N, int T,
-                                const int32_t *group_start, const int32_t *members, int p_lo, int p_hi, double *mant,
-                                int32_t *expo, double *gamma, double *gp, int32_t *pvalid, double *rows)
-{
-    const hipError_t e = dfb_lds_limit(dhmm_fb<NS>, lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(dhmm_fb<NS>, grid, dim3(64), lds, s, rec, n_states, nc, Smax, K, sym, len, N, T, group_start, members,
-                       p_lo, p_hi, mant, expo, gamma, gp, pvalid, rows);
-    return hipSuccess;
-}
-
 }  // namespace dsp
 
 extern "C" size_t dsp_dhmm_fb_workspace_bytes(int64_t C, int64_t N, int64_t P, int T, int Smax, int K)
 {
-    if (!dsp::dfb_in_plan(C, N, P, T, Smax, K)) return 0;
+    if (!dsp::dhmm_in_plan(C, N, P, T, Smax, K)) return 0;
     return dsp::dfb_plan(C, N, P, T, Smax, K).total();
 }
 
@@ -501,7 +392,7 @@ extern "C" int dsp_dhmm_forward(const double *pemit, const double *pstay, const 
                                 void *stream)
 {
     using namespace dsp;
-    if (!dfb_in_plan(C, N, 0, T, Smax, K)) return DSP_ERR_ARGS;
+    if (!dhmm_in_plan(C, N, 0, T, Smax, K)) return DSP_ERR_ARGS;
     if (N == 0 || (!mant && !expo && !label)) return DSP_OK;
     if (!sym || !len || (C > 0 && (!pemit || !pstay || !padv || !n_states))) return DSP_ERR_ARGS;
     const DfbPlan pl = dfb_plan(C, N, 0, T, Smax, K);
@@ -513,20 +404,21 @@ extern "C" int dsp_dhmm_forward(const double *pemit, const double *pstay, const 
     if (C > 0) {
         double *rec = (double *)ws;
         const int NS = pl.NS;
-        const size_t R = dfb_record(K, NS), lds = dfb_lds_bytes(K, NS);
-        hipLaunchKernelGGL(dhmm_fb_pack, csr_grid(C * (int64_t)R), dim3(256), 0, s, pemit, pstay, padv, n_states, C, Smax, K,
+        const size_t R = dhmm_record(K, NS), lds = dhmm_lds_bytes(K, NS);
+        hipLaunchKernelGGL(dhmm_pack, csr_grid(C * (int64_t)R), dim3(256), 0, s, pemit, pstay, padv, n_states, C, Smax, K,
                            NS, rec);
-        for (int64_t c0 = 0; c0 < C; c0 += DFB_GCHUNK) {
-            const int64_t nc = std::min<int64_t>(DFB_GCHUNK, C - c0);
-            const dim3 grid((unsigned)dfb_waves(nc * ((N + 63) / 64), T, NS, false));
+        for (int64_t c0 = 0; c0 < C; c0 += HMM_GCHUNK) {
+            const int64_t nc = std::min<int64_t>(HMM_GCHUNK, C - c0);
+            const dim3 grid((unsigned)csr_waves(nc * ((N + 63) / 64), 0));
             const double *rc = rec + (size_t)c0 * R;
-            hipError_t e;
-            if (NS == 8)
-                e = dfb_launch_fwd<8>(grid, lds, s, rc, n_states + c0, (int)c0, (int)nc, C, Smax, K, sym, len, N, T, mant, expo);
-            else if (NS == 16)
-                e = dfb_launch_fwd<16>(grid, lds, s, rc, n_states + c0, (int)c0, (int)nc, C, Smax, K, sym, len, N, T, mant, expo);
-            else
-                e = dfb_launch_fwd<32>(grid, lds, s, rc, n_states + c0, (int)c0, (int)nc, C, Smax, K, sym, len, N, T, mant, expo);
+            const hipError_t e = dhmm_with_slots(NS, [&](auto ns) {
+                constexpr int SLOTS = decltype(ns)::value;
+                const hipError_t err = dhmm_lds_limit(dhmm_fwd<SLOTS>, lds);
+                if (err == hipSuccess)
+                    hipLaunchKernelGGL(dhmm_fwd<SLOTS>, grid, dim3(64), lds, s, rc, n_states + c0, (int)c0, (int)nc, C, Smax, K, sym,
+                                       len, N, T, mant, expo);
+                return err;
+            });
             if (e != hipSuccess) return DSP_ERR_HIP + (int)e;
         }
     }
@@ -541,7 +433,7 @@ extern "C" int dsp_dhmm_expect(const double *pemit, const double *pstay, const d
                                void *stream)
 {
     using namespace dsp;
-    if (!dfb_in_plan(C, N, P, T, Smax, K)) return DSP_ERR_ARGS;
+    if (!dhmm_in_plan(C, N, P, T, Smax, K)) return DSP_ERR_ARGS;
     if (C == 0) return DSP_OK;
     if (!pemit || !pstay || !padv || !n_states || !group_start || !occ_emit || !n_valid || (P > 0 && !members) ||
         (N > 0 && (!sym || !len)))
@@ -553,31 +445,30 @@ extern "C" int dsp_dhmm_expect(const double *pemit, const double *pstay, const d
     double *rec = (double *)ws, *rows = (double *)(ws + pl.rec), *gp = (double *)(ws + pl.rec + pl.rows);
     int32_t *pvalid = (int32_t *)(ws + pl.rec + pl.rows + pl.gp);
     const int NS = pl.NS;
-    const size_t R = dfb_record(K, NS), lds = dfb_lds_bytes(K, NS);
+    const size_t R = dhmm_record(K, NS), lds = dhmm_lds_bytes(K, NS);
     const dim3 block(256);
-    hipLaunchKernelGGL(dhmm_fb_zero, csr_grid(C * Smax * (int64_t)K + C), block, 0, s, occ_emit, C * Smax * (int64_t)K, n_valid, C);
+    hipLaunchKernelGGL((csr_zero<double, int32_t>), csr_grid(C * Smax * (int64_t)K + C), block, 0, s, occ_emit,
+                       C * Smax * (int64_t)K, n_valid, C);
     if (P == 0) return dtw_launch_status();
     if (gamma)
-        hipLaunchKernelGGL(dhmm_fb_zero, csr_grid(P * T * Smax), block, 0, s, gamma, P * T * Smax, (int32_t *)nullptr, (int64_t)0);
-    hipLaunchKernelGGL(dhmm_fb_pack, csr_grid(C * (int64_t)R), block, 0, s, pemit, pstay, padv, n_states, C, Smax, K, NS, rec);
+        hipLaunchKernelGGL((csr_zero<double, int32_t>), csr_grid(P * T * Smax), block, 0, s, gamma, P * T * Smax, nullptr, 0);
+    hipLaunchKernelGGL(dhmm_pack, csr_grid(C * (int64_t)R), block, 0, s, pemit, pstay, padv, n_states, C, Smax, K, NS, rec);
     for (int64_t p_lo = 0; p_lo < P; p_lo += pl.PC) {
         const int64_t p_hi = std::min<int64_t>(P, p_lo + pl.PC);
         const int64_t cells = (p_hi - p_lo) * K * NS;
-        hipLaunchKernelGGL(dhmm_fb_zero, csr_grid(cells), block, 0, s, gp, cells, (int32_t *)nullptr, (int64_t)0);
-        for (int64_t c0 = 0; c0 < C; c0 += DFB_GCHUNK) {
-            const int64_t nc = std::min<int64_t>(DFB_GCHUNK, C - c0);
-            const dim3 grid((unsigned)std::min(pl.G, dfb_waves((p_hi - p_lo) / 64 + nc, T, NS, true)));
+        hipLaunchKernelGGL((csr_zero<double, int32_t>), csr_grid(cells), block, 0, s, gp, cells, nullptr, 0);
+        for (int64_t c0 = 0; c0 < C; c0 += HMM_GCHUNK) {
+            const int64_t nc = std::min<int64_t>(HMM_GCHUNK, C - c0);
+            const dim3 grid((unsigned)std::min(pl.G, csr_waves((p_hi - p_lo) / 64 + nc, dfb_rows_bytes(T, NS))));
             const double *rc = rec + (size_t)c0 * R;
-            hipError_t e;
-            if (NS == 8)
-                e = dfb_launch_fb<8>(grid, lds, s, rc, n_states + c0, (int)nc, Smax, K, sym, len, N, T, group_start + c0, members,
-                                     (int)p_lo, (int)p_hi, mant, expo, gamma, gp, pvalid, rows);
-            else if (NS == 16)
-                e = dfb_launch_fb<16>(grid, lds, s, rc, n_states + c0, (int)nc, Smax, K, sym, len, N, T, group_start + c0, members,
-                                      (int)p_lo, (int)p_hi, mant, expo, gamma, gp, pvalid, rows);
-            else
-                e = dfb_launch_fb<32>(grid, lds, s, rc, n_states + c0, (int)nc, Smax, K, sym, len, N, T, group_start + c0, members,
-                                      (int)p_lo, (int)p_hi, mant, expo, gamma, gp, pvalid, rows);
+            const hipError_t e = dhmm_with_slots(NS, [&](auto ns) {
+                constexpr int SLOTS = decltype(ns)::value;
+                const hipError_t err = dhmm_lds_limit(dhmm_fb<SLOTS>, lds);
+                if (err == hipSuccess)
+                    hipLaunchKernelGGL(dhmm_fb<SLOTS>, grid, dim3(64), lds, s, rc, n_states + c0, (int)nc, Smax, K, sym, len, N, T,
+                                       group_start + c0, members, (int)p_lo, (int)p_hi, mant, expo, gamma, gp, pvalid, rows);
+                return err;
+            });
             if (e != hipSuccess) return DSP_ERR_HIP + (int)e;
         }
         hipLaunchKernelGGL(dhmm_fb_sum, csr_grid(C * (int64_t)K * NS), block, 0, s, n_states, C, Smax, K, NS, group_start,

@@ -39,7 +39,7 @@
 //              whatever P is.
 //   dba_sums   a thread per (pair, frame, channel): S_k from the pair's ranges, all pairs in parallel.
 //   dba_accumulate / dba_finish   a thread per (template, frame, channel): acc = acc + S_k over the
-//              chunk's pairs in list order, then the division; csr_pairs.h's csr_zero_counts zeroes
+//              chunk's pairs in list order, then the division; csr_pairs.h's csr_zero zeroes
 //              the counts first.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -327,7 +327,7 @@ extern "C" int dsp_dtw_dba_update(const double *tmpl, const int32_t *len_t, int6
         const int64_t nc = std::min(pl.nc, C - c0), elems = nc * Tt * F;
         const dim3 grid = dsp::csr_grid(elems), block(256);
         double *out = tmpl_out + c0 * Tt * F, *in = inertia ? inertia + c0 : nullptr;
-        hipLaunchKernelGGL(dsp::csr_zero_counts, grid, block, 0, s, cnt, elems, nullptr, 0);
+        hipLaunchKernelGGL((dsp::csr_zero<int32_t, int32_t>), grid, block, 0, s, cnt, elems, nullptr, 0);
         for (int64_t p_lo = 0; p_lo < P; p_lo += pl.pc) {
             const int64_t p_hi = std::min(P, p_lo + pl.pc);
             const int rc = dsp::align_launch(s, pl, workspace, p_lo == 0, tmpl, len_t, c0, nc, Tt, seqs, len_s, N, Ts,

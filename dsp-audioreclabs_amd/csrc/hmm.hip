@@ -46,15 +46,14 @@
 //              path every row (a model is 32 (2 F + 3) doubles: more SGPRs than a wave has).  4 F + 4
 //              fp64 instructions per cell.  DIR: one bit per cell (b < a), a compare and a carry shift;
 //              a row is one 32-bit word per lane, stored [row][lane] in the wave's area of the
-//              workspace; each lane then walks its own path back (at most n - 1 steps, the row only
-//              decreases, so the walk ends inside the pair's words whatever the bits hold).
+//              workspace; each lane then walks its own path back (hmm_internal.h's hmm_walk_back).
 //              The tiles come from csr_pairs.h's csr_walk, dtw_align_dp's walk over the CSR list
 //              (dsp_hmm_score's "every model against all N": the walk without a list).
 //   csr_label  (csr_pairs.h) smallest score per sequence, ties to the smaller index, -1 when every
 //              score is +inf.
 //   hmm_pairs / hmm_sums / hmm_accumulate / hmm_finish   the re-estimation, as dba_sums /
 //              dba_accumulate / dba_finish: per-pair sums in parallel, then the ordered adds with the
-//              loads of 16 members issued together; csr_pairs.h's csr_zero_counts zeroes the counts.
+//              loads of 16 members issued together; csr_pairs.h's csr_zero zeroes the counts.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -63,15 +62,11 @@
 #include "csr_pairs.h"
 #include "dsp_audiorec.h"
 #include "dtw_internal.h"
+#include "hmm_internal.h"
 
 namespace dsp {
 
-static constexpr int HMM_SMAX = 32;                      // states a lane keeps in registers
-static constexpr int64_t HMM_CMAX = 1 << 20;             // models in a set at most
-static constexpr int HMM_GCHUNK = 1024;                  // models per launch at most
-static constexpr size_t HMM_WAVE_CAP = 256u << 20;       // bytes of direction words per launch
-static constexpr size_t HMM_SUMS_CAP = 128u << 20;       // bytes of X_k, Q_k and frame counts per pair chunk
-static constexpr int HMM_BATCH = 16;                     // members whose loads an accumulate thread keeps in flight
+static constexpr size_t HMM_SUMS_CAP = 128u << 20;  // bytes of X_k, Q_k and frame counts per pair chunk
 
 // rec [C][32][2 F + 3], see above; a model with an invalid n_states gets zeros (never read)
 __global__ __launch_bounds__(256) void hmm_pack(const double *__restrict__ mu, const double *__restrict__ w,
@@ -210,25 +205,13 @@ __global__ __launch_bounds__(64) void hmm_dp(const double *__restrict__ rec, con
                      res = hmm_sweep<F, DIR>(rc, HMM_SMAX - S, x + (int64_t)ln.row * T * F, n, ln.lmax, dir);
                  if (!ln.inr) return;
                  if (score) score[group_start ? p : p * C + c0 + cg] = res;
-                 if (!DIR || !seg) return;
-                 int32_t *__restrict__ ps = seg + p * Smax;
-                 int filled = 0;
-                 if (res < INFINITY) {
-                     // the lane's own walk back: state s is slot s + 32 - S, that bit of a row's word
-                     int s = S - 1;
-                     for (int r = n - 1; r >= 1 && s > 0; r--)
-                         if ((dir[(size_t)r * 64] >> (s + HMM_SMAX - S)) & 1) ps[s--] = r;
-                     for (; s > 0; s--) ps[s] = s;  // not reached with the sweep's own words
-                     ps[0] = 0;
-                     filled = S;
-                 }
-                 for (int i = filled; i < Smax; i++) ps[i] = -1;
+                 if (DIR && seg) hmm_walk_back(dir, n, S, HMM_SMAX, Smax, res < INFINITY, seg + p * Smax);
              });
 }
 
 // ---- re-estimation ----
-// A thread per pair of [p_lo, p_hi): its model (the group that holds p, by bisection of group_start)
-// and whether it is valid; plen [p - p_lo][s] = frames of state s, all 0 for a pair that is skipped.
+// A thread per pair of [p_lo, p_hi): its model (the group that holds p) and whether it is valid;
+// plen [p - p_lo][s] = frames of state s, all 0 for a pair that is skipped.
 __global__ __launch_bounds__(256) void hmm_pairs(const int32_t *__restrict__ n_states, int64_t C, int Smax,
                                                  const int32_t *__restrict__ len, int64_t N, int T,
                                                  const int32_t *__restrict__ group_start,
@@ -236,24 +219,13 @@ __global__ __launch_bounds__(256) void hmm_pairs(const int32_t *__restrict__ n_s
                                                  const int32_t *__restrict__ seg, int32_t *__restrict__ plen)
 {
     for (int64_t p = p_lo + (int64_t)blockIdx.x * 256 + threadIdx.x; p < p_hi; p += (int64_t)gridDim.x * 256) {
-        int64_t lo = 0, hi = C;  // the last c with group_start[c] <= p
-        while (hi - lo > 1) {
-            const int64_t mid = (lo + hi) / 2;
-            if (group_start[mid] <= p)
-                lo = mid;
-            else
-                hi = mid;
-        }
+        const int64_t lo = csr_group_of(group_start, C, p);
         const int S = n_states[lo], mem = members[p];
         const int32_t *__restrict__ ps = seg + p * Smax;
         int32_t *__restrict__ pl = plen + (p - p_lo) * Smax;
-        bool ok = S >= 1 && S <= Smax && mem >= 0 && mem < N && p < group_start[lo + 1];
-        int n = ok ? len[mem] : 0;
-        ok = ok && n >= 1 && n <= T && ps[0] == 0;
-        for (int s = 0; ok && s < S; s++) {
-            const int b = ps[s], e = s + 1 < S ? ps[s + 1] : n;
-            ok = b >= 0 && b < e && e <= n;
-        }
+        bool ok = S >= 1 && S <= Smax && mem >= 0 && mem < N && p >= group_start[lo] && p < group_start[lo + 1];
+        const int n = ok ? len[mem] : 0;
+        ok = ok && n >= 1 && n <= T && hmm_seg_ok(ps, S, n);
         for (int s = 0; s < Smax; s++) pl[s] = ok && s < S ? (s + 1 < S ? ps[s + 1] : n) - ps[s] : 0;
     }
 }
@@ -386,18 +358,13 @@ struct HmmPlan {
     size_t rec, dir, score, plen, sums, cnt;
     size_t total() const { return rec + dir + score + plen + 2 * sums + cnt; }
 };
-static int hmm_waves(int64_t tiles, int T, bool with_dir)
-{
-    const int64_t cap = with_dir ? std::max<int64_t>(1, (int64_t)(HMM_WAVE_CAP / ((size_t)T * 64 * 4))) : DTW_WAVES;
-    return (int)std::max<int64_t>(1, std::min<int64_t>(tiles, std::min<int64_t>(DTW_WAVES, cap)));
-}
 static HmmPlan hmm_plan(int64_t C, int64_t N, int64_t P, int T, int F, int Smax)
 {
     HmmPlan pl;
     pl.pc = std::max<int64_t>(1, std::min<int64_t>(P, (int64_t)(HMM_SUMS_CAP / ((size_t)Smax * (4 + 16 * F)))));
-    pl.G = hmm_waves(P / 64 + std::min<int64_t>(C, HMM_GCHUNK), T, true);
+    pl.G = csr_waves(P / 64 + std::min<int64_t>(C, HMM_GCHUNK), hmm_dir_bytes(T));
     pl.rec = up256((size_t)C * HMM_SMAX * (2 * F + 3) * 8);
-    pl.dir = up256((size_t)pl.G * T * 64 * 4);
+    pl.dir = up256(pl.G * hmm_dir_bytes(T));
     pl.score = up256((size_t)N * C * 8);
     pl.plen = up256((size_t)pl.pc * Smax * 4);
     pl.sums = up256((size_t)pl.pc * Smax * F * 8);
@@ -425,7 +392,7 @@ static int hmm_run(hipStream_t s, const HmmPlan &pl, void *ws, const double *mu,
     for (int64_t c0 = 0; c0 < C; c0 += HMM_GCHUNK) {
         const int64_t nc = std::min<int64_t>(HMM_GCHUNK, C - c0);
         const int64_t tiles = group_start ? P / 64 + nc : nc * ((N + 63) / 64);
-        const int G = DIR ? std::min(pl.G, hmm_waves(tiles, T, true)) : hmm_waves(tiles, T, false);
+        const int G = DIR ? std::min(pl.G, csr_waves(tiles, hmm_dir_bytes(T))) : csr_waves(tiles, 0);
         const double *rc = rec + (size_t)c0 * HMM_SMAX * R;
         const int32_t *gs = group_start ? group_start + c0 : nullptr;
         if (DIR) {
@@ -506,7 +473,7 @@ extern "C" int dsp_hmm_accumulate(const double *mu_prev, const double *var_prev,
     int32_t *cntf = (int32_t *)(wsp + pl.plen + 2 * pl.sums);
     const int64_t elems = C * Smax * F;
     const dim3 block(256);
-    hipLaunchKernelGGL(dsp::csr_zero_counts, dsp::csr_grid(elems + C), block, 0, s, cntf, elems, n_valid, C);
+    hipLaunchKernelGGL((dsp::csr_zero<int32_t, int32_t>), dsp::csr_grid(elems + C), block, 0, s, cntf, elems, n_valid, C);
     for (int64_t p_lo = 0; p_lo < P; p_lo += pl.pc) {
         const int64_t p_hi = std::min(P, p_lo + pl.pc), np = p_hi - p_lo;
         hipLaunchKernelGGL(dsp::hmm_pairs, dsp::csr_grid(np), block, 0, s, n_states, C, Smax, len, N, T, group_start,

@@ -48,7 +48,7 @@
 //              hmm_accumulate / hmm_finish: per-pair validity and per-cell frame counts, per-pair cell
 //              sums in parallel, then the ordered adds in list order with the loads of 16 members issued
 //              together, then the divide and the copy rule; pairs in chunks whose sums and counts fit
-//              128 MiB, csr_pairs.h's csr_zero_counts before the first.
+//              128 MiB, csr_pairs.h's csr_zero before the first.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -441,7 +441,7 @@ extern "C" int dsp_vq_accumulate(const double *cb_prev, const int32_t *n_codes, 
     int32_t *cntf = (int32_t *)(wsp + pl.pcnt + pl.pok + pl.sums);
     const int64_t elems = C * Kmax * F;
     const dim3 block(256);
-    hipLaunchKernelGGL(dsp::csr_zero_counts, dsp::csr_grid(elems + C), block, 0, s, cntf, elems, n_valid, C);
+    hipLaunchKernelGGL((dsp::csr_zero<int32_t, int32_t>), dsp::csr_grid(elems + C), block, 0, s, cntf, elems, n_valid, C);
     for (int64_t p_lo = 0; p_lo < P; p_lo += pl.pc) {
         const int64_t p_hi = std::min(P, p_lo + pl.pc), np = p_hi - p_lo;
         hipLaunchKernelGGL(dsp::vq_pairs, dsp::csr_grid(np), block, 0, s, n_codes, C, Kmax, len, N, T, group_start, members,

@@ -491,7 +491,34 @@ def dtw_barycenter(seqs, lengths, init, n_iter=10, window=None, check_finite=Tru
 HMM_MAX_STATES = 32  # states of one model at most (csrc/hmm.hip keeps them in registers)
 
 
-class HmmModelSet:
+class _HmmSet:
+    """What the left-to-right model sets share: ``_fields`` names the float64 arrays of the set in the order
+    the C ABI takes them (the first one [C, Smax, .]); n_states int32 [C] follows them."""
+    _fields = ()
+    _dev = None
+
+    @property
+    def shape(self):
+        return getattr(self, self._fields[0]).shape
+
+    def on_device(self, device):
+        """(the ``_fields`` arrays, n_states) as device tensors, uploaded once."""
+        import torch
+        if self._dev is None or self._dev[0].device != torch.device(device):
+            self._dev = tuple(_as_device(getattr(self, f), torch.float64, device) for f in self._fields)
+            self._dev += (_as_device(self.n_states, torch.int32, device),)
+        return self._dev
+
+
+def _hmm_p_stay(occ, n_valid, seen, trans_floor):
+    """(occ - n_valid) / occ clamped to [trans_floor, 1 - trans_floor]; 0.5 where not ``seen``.  occ [C, Smax]:
+    integer frame counts or float occupancies."""
+    of = np.where(seen, occ, 2).astype(np.float64)
+    p = (of - np.where(seen, n_valid[:, None], 1).astype(np.float64)) / of
+    return np.minimum(np.maximum(p, trans_floor), 1.0 - trans_floor)
+
+
+class HmmModelSet(_HmmSet):
     """C left-to-right Gaussian HMMs padded to Smax states, in the form ``dsp_hmm_score`` reads
     (include/dsp_audiorec.h): mean, var, w [C, Smax, F], g, stay, adv [C, Smax] float64 and n_states
     int32 [C], numpy arrays on the host.  This is the only place a logarithm is taken:
@@ -500,6 +527,8 @@ class HmmModelSet:
         stay = -log(p_stay);  adv = -log(1 - p_stay)
     Rows s >= n_states[c] are zeros.  A model with n_valid == 0 keeps ``prev``'s stay / adv (p_stay = 0.5
     without ``prev``)."""
+
+    _fields = ("mean", "w", "g", "stay", "adv")
 
     def __init__(self, mean, var, cnt, n_valid, n_states, trans_floor=1e-3, prev=None):
         mean, var = (_as_host(v, np.float64) for v in (mean, var))
@@ -523,27 +552,12 @@ class HmmModelSet:
         self.w = np.where(valid[:, :, None], 0.5 / v, 0.0)
         self.g = np.where(valid, 0.5 * np.cumsum(np.log((2.0 * np.pi) * v), axis=2)[:, :, -1], 0.0)
         seen = valid & (cnt > 0) & (n_valid[:, None] > 0)
-        cf = np.where(seen, cnt, 2).astype(np.float64)
-        p = (cf - np.where(seen, n_valid[:, None], 1).astype(np.float64)) / cf
-        p = np.minimum(np.maximum(p, trans_floor), 1.0 - trans_floor)
+        p = _hmm_p_stay(cnt, n_valid, seen, trans_floor)
         stay, adv = -np.log(p), -np.log(1.0 - p)
         if prev is not None:
             keep = (n_valid == 0)[:, None]
             stay, adv = np.where(keep, prev.stay, stay), np.where(keep, prev.adv, adv)
         self.stay, self.adv = np.where(valid, stay, 0.0), np.where(valid, adv, 0.0)
-        self._dev = None
-
-    @property
-    def shape(self):
-        return self.mean.shape
-
-    def on_device(self, device):
-        """(mu, w, g, stay, adv, n_states) as device tensors, uploaded once."""
-        import torch
-        if self._dev is None or self._dev[0].device != torch.device(device):
-            self._dev = tuple(_as_device(a, torch.float64, device) for a in (self.mean, self.w, self.g, self.stay, self.adv))
-            self._dev += (_as_device(self.n_states, torch.int32, device),)
-        return self._dev
 
 
 _HMM_SHAPE = "unsupported HMM shape (1 <= F <= 8, 1 <= T <= 1024, 1 <= Smax <= %d)" % HMM_MAX_STATES
@@ -799,7 +813,37 @@ def vq_repair_empty(cb, cnt, n_codes, eps):
 DHMM_MAX_SYMBOLS = 256  # symbols of the shared alphabet at most (csrc/dhmm.hip stages a model's table into LDS)
 
 
-class DhmmModelSet:
+def _dhmm_check(C, Smax, K, n_states):
+    if n_states.shape != (C,) or not 1 <= Smax <= HMM_MAX_STATES or not 1 <= K <= DHMM_MAX_SYMBOLS:
+        raise ValueError("n_states must be [C], 1 <= Smax <= %d, 1 <= K <= %d" % (HMM_MAX_STATES, DHMM_MAX_SYMBOLS))
+    if C and (n_states.min() < 1 or n_states.max() > Smax):
+        raise ValueError("n_states must lie in [1, %d]" % Smax)
+
+
+def _dhmm_count_args(C, Smax, K, n_valid, n_states, alpha, trans_floor):
+    """The checks both discrete sets make on what they are built from; (valid [C, Smax]: the states each
+    model has, alpha as float64)."""
+    _dhmm_check(C, Smax, K, n_states)
+    if n_valid.shape != (C,):
+        raise ValueError("n_valid must be [C]")
+    if not (alpha > 0.0 and np.isfinite(alpha)):
+        raise ValueError("alpha must be a positive number")
+    if not 0.0 < trans_floor < 0.5:
+        raise ValueError("trans_floor must lie in (0, 0.5)")
+    return np.arange(Smax)[None, :] < n_states[:, None], np.float64(alpha)
+
+
+def _dhmm_hand_built(table, stay, adv, n_states, names):
+    """from_arrays' operands on the host, shapes checked: (table [C, Smax, K], stay, adv [C, Smax], n_states int32 [C])"""
+    table, stay, adv = (np.array(_as_host(v, np.float64)) for v in (table, stay, adv))
+    n_states = _as_host(n_states).astype(np.int64).reshape(-1)
+    if table.ndim != 3 or stay.shape != table.shape[:2] or adv.shape != table.shape[:2]:
+        raise ValueError("%s must be [C, Smax, K] and %s, %s [C, Smax]" % names)
+    _dhmm_check(*table.shape, n_states)
+    return table, stay, adv, n_states.astype(np.int32)
+
+
+class DhmmModelSet(_HmmSet):
     """C left-to-right HMMs with discrete observations padded to Smax states over an alphabet of K
     symbols, in the form ``dsp_dhmm_score`` reads (include/dsp_audiorec.h): emit float64 [C, Smax, K],
     stay, adv float64 [C, Smax] and n_states int32 [C], numpy arrays on the host, built from the counts
@@ -811,26 +855,18 @@ class DhmmModelSet:
     are zeros.  A model with n_valid == 0 keeps ``prev``'s stay / adv (p_stay = 0.5 without ``prev``); its
     emissions come from its (all-zero) counts like any other's.  ``from_arrays`` takes a hand-built set."""
 
+    _fields = ("emit", "stay", "adv")
+
     def __init__(self, cnt_emit, cnt, n_valid, n_states, alpha=0.5, trans_floor=1e-3, prev=None):
         cnt_emit, cnt, n_valid, n_states = (_as_host(v).astype(np.int64) for v in (cnt_emit, cnt, n_valid, n_states))
         if cnt_emit.ndim != 3 or cnt.shape != cnt_emit.shape[:2]:
             raise ValueError("cnt_emit must be [C, Smax, K] and cnt [C, Smax]")
         C, Smax, K = cnt_emit.shape
-        self._check(C, Smax, K, n_states)
-        if n_valid.shape != (C,):
-            raise ValueError("n_valid must be [C]")
-        if not (alpha > 0.0 and np.isfinite(alpha)):
-            raise ValueError("alpha must be a positive number")
-        if not 0.0 < trans_floor < 0.5:
-            raise ValueError("trans_floor must lie in (0, 0.5)")
-        alpha = np.float64(alpha)
-        valid = np.arange(Smax)[None, :] < n_states[:, None]
+        valid, alpha = _dhmm_count_args(C, Smax, K, n_valid, n_states, alpha, trans_floor)
         den = cnt.astype(np.float64) + alpha * np.float64(K)
         emit = -np.log((cnt_emit.astype(np.float64) + alpha) / den[:, :, None])
         seen = valid & (cnt > 0) & (n_valid[:, None] > 0)
-        cf = np.where(seen, cnt, 2).astype(np.float64)
-        p = (cf - np.where(seen, n_valid[:, None], 1).astype(np.float64)) / cf
-        p = np.minimum(np.maximum(p, trans_floor), 1.0 - trans_floor)
+        p = _hmm_p_stay(cnt, n_valid, seen, trans_floor)
         stay, adv = -np.log(p), -np.log(1.0 - p)
         if prev is not None:
             keep = (n_valid == 0)[:, None]
@@ -838,48 +874,23 @@ class DhmmModelSet:
         self.n_states = n_states.astype(np.int32)
         self.emit = np.where(valid[:, :, None], emit, 0.0)
         self.stay, self.adv = np.where(valid, stay, 0.0), np.where(valid, adv, 0.0)
-        self._dev = None
-
-    @staticmethod
-    def _check(C, Smax, K, n_states):
-        if n_states.shape != (C,) or not 1 <= Smax <= HMM_MAX_STATES or not 1 <= K <= DHMM_MAX_SYMBOLS:
-            raise ValueError("n_states must be [C], 1 <= Smax <= %d, 1 <= K <= %d" % (HMM_MAX_STATES, DHMM_MAX_SYMBOLS))
-        if C and (n_states.min() < 1 or n_states.max() > Smax):
-            raise ValueError("n_states must lie in [1, %d]" % Smax)
 
     @classmethod
     def from_arrays(cls, emit, stay, adv, n_states):
         """A hand-built set: emit [C, Smax, K], stay, adv [C, Smax] as they are (finite or +inf, never NaN,
         never -inf), n_states [C]."""
-        emit, stay, adv = (np.array(_as_host(v, np.float64)) for v in (emit, stay, adv))
-        n_states = _as_host(n_states).astype(np.int64).reshape(-1)
-        if emit.ndim != 3 or stay.shape != emit.shape[:2] or adv.shape != emit.shape[:2]:
-            raise ValueError("emit must be [C, Smax, K] and stay, adv [C, Smax]")
-        cls._check(*emit.shape, n_states)
-        for v in (emit, stay, adv):
+        self = cls.__new__(cls)
+        self.emit, self.stay, self.adv, self.n_states = _dhmm_hand_built(emit, stay, adv, n_states, ("emit", "stay", "adv"))
+        for v in (self.emit, self.stay, self.adv):
             if np.isnan(v).any() or (v == -np.inf).any():
                 raise ValueError("costs must be finite or +inf")
-        self = cls.__new__(cls)
-        self.emit, self.stay, self.adv, self.n_states, self._dev = emit, stay, adv, n_states.astype(np.int32), None
         return self
-
-    @property
-    def shape(self):
-        return self.emit.shape
-
-    def on_device(self, device):
-        """(emit, stay, adv, n_states) as device tensors, uploaded once."""
-        import torch
-        if self._dev is None or self._dev[0].device != torch.device(device):
-            self._dev = tuple(_as_device(a, torch.float64, device) for a in (self.emit, self.stay, self.adv))
-            self._dev += (_as_device(self.n_states, torch.int32, device),)
-        return self._dev
 
 
 DHMM_MIN_PROB = 2.0 ** -300  # the smallest non-zero probability dsp_dhmm_forward reads (include/dsp_audiorec.h)
 
 
-class DhmmProbSet:
+class DhmmProbSet(_HmmSet):
     """The model set of ``DhmmModelSet`` in the PROBABILITY domain, in the form ``dsp_dhmm_forward`` and
     ``dsp_dhmm_expect`` read (include/dsp_audiorec.h): pemit float64 [C, Smax, K], pstay, padv float64
     [C, Smax] and n_states int32 [C], numpy arrays on the host, built from the expected counts of
@@ -893,63 +904,38 @@ class DhmmProbSet:
     given.  Rows s >= n_states[c] are zeros.  ``from_arrays`` takes a hand-built set; ``to_costs`` gives the
     ``DhmmModelSet`` of the same models, which feeds dhmm_score, dhmm_align and dhmm_decode unchanged."""
 
+    _fields = ("pemit", "pstay", "padv")
+
     def __init__(self, occ_emit, n_valid, n_states, alpha=0.5, trans_floor=1e-3, prev=None):
         occ_emit = np.asarray(_as_host(occ_emit), np.float64)
         n_valid, n_states = (_as_host(v).astype(np.int64) for v in (n_valid, n_states))
         if occ_emit.ndim != 3:
             raise ValueError("occ_emit must be [C, Smax, K]")
         C, Smax, K = occ_emit.shape
-        DhmmModelSet._check(C, Smax, K, n_states)
-        if n_valid.shape != (C,):
-            raise ValueError("n_valid must be [C]")
-        if not (alpha > 0.0 and np.isfinite(alpha)):
-            raise ValueError("alpha must be a positive number")
-        if not 0.0 < trans_floor < 0.5:
-            raise ValueError("trans_floor must lie in (0, 0.5)")
+        valid, alpha = _dhmm_count_args(C, Smax, K, n_valid, n_states, alpha, trans_floor)
         if not (np.isfinite(occ_emit).all() and (occ_emit >= 0.0).all()):
             raise ValueError("occ_emit must be finite and non-negative")
-        alpha = np.float64(alpha)
-        valid = np.arange(Smax)[None, :] < n_states[:, None]
         occ = np.add.accumulate(occ_emit, axis=2)[:, :, -1]  # sequential, ascending k: np.sum adds pairwise
         pemit = (occ_emit + alpha) / (occ + alpha * np.float64(K))[:, :, None]
         seen = valid & (occ > 0.0) & (n_valid[:, None] > 0)
-        of = np.where(seen, occ, 2.0)
-        p = (of - np.where(seen, n_valid[:, None], 1).astype(np.float64)) / of
-        p = np.minimum(np.maximum(p, trans_floor), 1.0 - trans_floor)
+        p = _hmm_p_stay(occ, n_valid, seen, trans_floor)
         if prev is not None:
             p = np.where((n_valid == 0)[:, None], prev.pstay, p)
         self.n_states = n_states.astype(np.int32)
         self.pemit = np.where(valid[:, :, None], pemit, 0.0)
         self.pstay, self.padv = np.where(valid, p, 0.0), np.where(valid, 1.0 - p, 0.0)
-        self._dev = None
 
     @classmethod
     def from_arrays(cls, pemit, pstay, padv, n_states):
         """A hand-built set: pemit [C, Smax, K], pstay, padv [C, Smax] as they are (every entry 0.0 or in
         [2^-300, 1], never NaN), n_states [C]."""
-        pemit, pstay, padv = (np.array(_as_host(v, np.float64)) for v in (pemit, pstay, padv))
-        n_states = _as_host(n_states).astype(np.int64).reshape(-1)
-        if pemit.ndim != 3 or pstay.shape != pemit.shape[:2] or padv.shape != pemit.shape[:2]:
-            raise ValueError("pemit must be [C, Smax, K] and pstay, padv [C, Smax]")
-        DhmmModelSet._check(*pemit.shape, n_states)
-        for v in (pemit, pstay, padv):
+        self = cls.__new__(cls)
+        self.pemit, self.pstay, self.padv, self.n_states = _dhmm_hand_built(pemit, pstay, padv, n_states,
+                                                                            ("pemit", "pstay", "padv"))
+        for v in (self.pemit, self.pstay, self.padv):
             if not ((v == 0.0) | ((v >= DHMM_MIN_PROB) & (v <= 1.0))).all():
                 raise ValueError("probabilities must be 0.0 or lie in [2^-300, 1]")
-        self = cls.__new__(cls)
-        self.pemit, self.pstay, self.padv, self.n_states, self._dev = pemit, pstay, padv, n_states.astype(np.int32), None
         return self
-
-    @property
-    def shape(self):
-        return self.pemit.shape
-
-    def on_device(self, device):
-        """(pemit, pstay, padv, n_states) as device tensors, uploaded once."""
-        import torch
-        if self._dev is None or self._dev[0].device != torch.device(device):
-            self._dev = tuple(_as_device(a, torch.float64, device) for a in (self.pemit, self.pstay, self.padv))
-            self._dev += (_as_device(self.n_states, torch.int32, device),)
-        return self._dev
 
     def to_costs(self):
         """The ``DhmmModelSet`` of the same models: -log p entry by entry, +inf for 0.0 (rows s >= n_states[c]
