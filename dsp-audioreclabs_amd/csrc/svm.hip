@@ -28,7 +28,7 @@
 // both sides,
 //   bound_p = 2^-52 [ (n_i + n_j + 4) (B_q + |b_p|) + 2 SVC_EXP_ULPS B_q + (D + 4) A / e ]
 // and a query is certified when every pair has |dec_p| > SVC_SAFETY bound_p.  The caller answers
-// the others with libsvm itself.
+// the others with libsvm itself.  A row holding an inf or a NaN is never certified (svc_main).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -46,9 +46,12 @@ static constexpr double SVC_EXP_ULPS = 4.0;  // allowance per exp, each side (oc
 static constexpr double SVC_SAFETY = 4.0;
 static constexpr double SVC_INV_E = 0.36787944117144233;  // max x e^-x, rounded up
 
-// cmax[s] = max_r |coef[r][s]|; asum[0] = sum_s cmax[s] (one workgroup, fixed order)
+// cmax[s] = max_r |coef[r][s]|; asum[0] = sum_s cmax[s] (one workgroup, fixed order).  It also zeroes
+// the uncertified count for svc_finish: a kernel's store, not hipMemsetAsync, so that a captured call
+// is a plain chain of kernels (after a graph replay the memset's counter did not read as zeroed).
 __global__ __launch_bounds__(256) void svc_prep(const double *__restrict__ coef, int64_t nSV, int C,
-                                                double *__restrict__ cmax, double *__restrict__ asum)
+                                                double *__restrict__ cmax, double *__restrict__ asum,
+                                                int32_t *__restrict__ uncertified)
 {
     __shared__ double red[256];
     double a = 0.0;
@@ -64,7 +67,10 @@ __global__ __launch_bounds__(256) void svc_prep(const double *__restrict__ coef,
         if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
         __syncthreads();
     }
-    if (threadIdx.x == 0) asum[0] = red[0];
+    if (threadIdx.x == 0) {
+        asum[0] = red[0];
+        uncertified[0] = 0;
+    }
 }
 
 struct SvcArgs {
@@ -124,13 +130,24 @@ __global__ __launch_bounds__(SVC_T) void svc_main(const SvcArgs a)
 #pragma unroll
         for (int d = 0; d < DP; d++) q[d] = d < D ? qrow[d] : 0.0;
     }
+    // A row holding an inf would give d^2 = inf, K_s = 0 and dec_p = intercept[p] with a small bound:
+    // certified, where libsvm's caller refuses the row.  x * 0 is NaN for an inf and for a NaN and +0
+    // (after the add) for every finite x, so the lane's class blocks and B_q start from `poison`
+    // instead of zero: a finite row keeps its bits, any other gets NaN in every dec_p and in its bound.
+    double poison = 0.0;
+    if constexpr (!HD) {
+#pragma unroll
+        for (int d = 0; d < DP; d++) poison = fma(q[d], 0.0, poison);
+    } else {
+        for (int d = 0; d < D; d++) poison = fma(qrow[d], 0.0, poison);
+    }
 
     int64_t start = 0;
     for (int c = 0; c < C; c++) {
         const int n = a.nsup[c];
-        double total[CR], btotal = 0.0;
+        double total[CR], btotal = poison;
 #pragma unroll
-        for (int r = 0; r < CR; r++) total[r] = 0.0;
+        for (int r = 0; r < CR; r++) total[r] = poison;
         for (int g = g0; g < g1; g++) {
             int64_t lo, hi;
             svc_segment(start, n, g, a.G, a.nSV, lo, hi);
@@ -356,8 +373,8 @@ extern "C" int dsp_svc_predict(const double *sv, const int32_t *n_support, const
     hipStream_t s = (hipStream_t)stream;
     char *ws = (char *)workspace;
     double *cmax = (double *)(ws + l.cmax), *asum = (double *)(ws + l.asum);
-    if (hipMemsetAsync(ws + l.asum, 0, 256, s) != hipSuccess) return DSP_ERR_HIP;
-    hipLaunchKernelGGL(dsp::svc_prep, dim3(1), dim3(256), 0, s, dual_coef, nSV, C, cmax, asum);
+    hipLaunchKernelGGL(dsp::svc_prep, dim3(1), dim3(256), 0, s, dual_coef, nSV, C, cmax, asum,
+                       (int32_t *)(ws + l.count));
 
     dsp::SvcArgs a;
     a.sv = sv, a.coef = dual_coef, a.cmax = cmax, a.query = query, a.nsup = n_support;

@@ -131,10 +131,11 @@ class TraditionalClassifier:
         return self
 
     # -- SVC, Naive Bayes and Decision Tree on the device (models.py:37-47, :52-58) -------------
-    def _certified(self, X, method, answer, redo=True, **outputs):
+    def _certified(self, X, method, answer, redo=None, **outputs):
         """``method`` (the model's predict, apply or _decision_function) of X, computed on the device:
         ``answer`` of the query's outputs as numpy arrays, and ``method``'s own result for the rows the
-        device did not settle.  A model or rows outside the kernel's plan are ``method``'s entirely."""
+        device did not settle, or for the rows ``redo`` of the outputs marks.  A model or rows outside
+        the kernel's plan are ``method``'s entirely."""
         Index, unsettled = _DEVICE[self.classifier_type]
         m = self.model
         if not Index.in_plan(m, X):
@@ -150,7 +151,9 @@ class TraditionalClassifier:
         rows = np.flatnonzero(unsettled(*out))
         self.last_predict_stats = {'device': True, 'uncertified': len(rows)}  # (before method may raise)
         y = answer(*out)
-        if redo and len(rows):
+        if redo is not None:
+            rows = np.flatnonzero(redo(*out))
+        if len(rows):
             y[rows] = method(_as_host(X[rows]))
         return y
 
@@ -159,8 +162,11 @@ class TraditionalClassifier:
         scikit-learn's flipped sign for two classes).  SVM only."""
         if self.classifier_type != 'svm':
             raise AttributeError("decision_function is the SVM's")
-        # dec is within its derived bound on every row, certified or not: nothing is redone
-        return self._certified(X, self.model._decision_function, redo=False, with_dec=True,
+        # dec is within its derived bound on every row, certified or not, so a near tie is not redone.
+        # A row with a NaN or an inf comes back as NaN in every dec_p (csrc/svm.hip): the model is
+        # asked for the rows whose dec is not finite, and raises for them as SVC.decision_function does.
+        return self._certified(X, self.model._decision_function, with_dec=True,
+                               redo=lambda pred, dec, certified: ~np.isfinite(dec).all(axis=1),
                                answer=lambda pred, dec, certified: -dec.ravel() if dec.shape[1] == 1 else dec)
 
     def apply(self, X):

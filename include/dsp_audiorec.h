@@ -312,7 +312,8 @@ int dsp_mlp_dropout_mask(uint32_t seed, int64_t step, int layer, int rows, int w
  *            rounding of the squared distance), so the vote is libsvm's; 0: the
  *            caller answers that row with libsvm itself.  Equal inputs give equal bits, and a row's
  *            dec bits do not depend on Nq or on the row's position (fixed summation order, no atomics
- *            on floating-point data).
+ *            on floating-point data).  A query row holding an inf or a NaN (scikit-learn refuses it)
+ *            comes back with NaN in every dec_p and certified = 0, and is counted.
  * workspace  device scratch of dsp_svc_workspace_bytes(nSV, Nq, D, C) bytes (0: sizes outside the
  *            plan); at dsp_svc_workspace_uncertified_offset an int32 is left holding the number of
  *            uncertified rows.
