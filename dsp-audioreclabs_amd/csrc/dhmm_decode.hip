@@ -27,7 +27,8 @@
 // forced), and when no word can end at n-1.
 //
 // Kernels:
-//   dhmm_decode_pack  the set transposed into the workspace for a wave whose LANE is the word model:
+//   dhmm_decode_pack  (hmm_internal.h, with the plan of its three parts; dhmm_force.hip launches it too) the
+//              set transposed into the workspace for a wave whose LANE is the word model:
 //              tab [K][NS][64] doubles, NS = 8, 16 or 32 slots as in dhmm.hip and END-aligned (state s of a
 //              model of S states in slot s + NS - S, so every model's exit is slot NS - 1); the slots before
 //              a model's first state, a model with an invalid n_states and the lanes c >= C hold +inf, so
@@ -62,59 +63,13 @@ namespace dsp {
 
 static constexpr int DHMM_DECODE_WAVES = 8192;  // persistent waves per launch at most (32 per CU, all that can be resident)
 
-// doubles / bytes of the workspace's three parts
-struct DecodePlan {
-    int NS;
-    size_t tab, tr, j0;
-    size_t total() const { return tab + tr + j0; }
-};
 static bool decode_in_plan(int64_t C, int64_t N, int T, int Smax, int K)
 {
     return C >= 1 && C <= DSP_DHMM_DECODE_MAX_MODELS && N >= 0 && N < 0x7fffffff && Smax >= 1 && Smax <= DHMM_SMAX &&
            K >= 1 && K <= DHMM_KMAX && T >= 1 && T <= DTW_TMAX;
 }
-static DecodePlan decode_plan(int Smax, int K)
-{
-    DecodePlan pl;
-    pl.NS = dhmm_slots(Smax);
-    pl.tab = up256((size_t)K * pl.NS * 64 * 8);
-    pl.tr = up256((size_t)pl.NS * 64 * 16);
-    pl.j0 = up256(64 * 4);
-    return pl;
-}
 // dynamic LDS: 16 bytes per frame, then at 32 slots the transitions
 static size_t decode_lds_bytes(int T, int NS) { return (size_t)T * 16 + (NS == 32 ? (size_t)NS * 64 * 16 : 0); }
-
-__global__ __launch_bounds__(256) void dhmm_decode_pack(const double *__restrict__ emit, const double *__restrict__ stay,
-                                                        const double *__restrict__ adv, const int32_t *__restrict__ n_states,
-                                                        const double *__restrict__ enter, int C, int Smax, int K, int NS,
-                                                        double *__restrict__ tab, double2 *__restrict__ tr,
-                                                        int32_t *__restrict__ j0)
-{
-    const int ntab = K * NS * 64, ntr = NS * 64;
-    for (int e = (int)blockIdx.x * 256 + (int)threadIdx.x; e < ntab + ntr + 64; e += (int)gridDim.x * 256) {
-        const int c = e % 64;
-        const int S = c < C ? n_states[c] : 0;
-        const bool ok = S >= 1 && S <= Smax;
-        if (e >= ntab + ntr) {
-            j0[c] = ok ? NS - S : NS;
-            continue;
-        }
-        const int j = (e / 64) % NS, s = ok ? j - (NS - S) : -1;
-        const bool in = s >= 0;
-        const int64_t cs = (int64_t)c * Smax + s;
-        if (e < ntab) {
-            tab[e] = in ? emit[cs * K + e / (NS * 64)] : (double)INFINITY;
-        } else {
-            double2 v = make_double2(0.0, 0.0);
-            if (in) {
-                v.x = stay[cs];
-                v.y = s > 0 ? adv[cs - 1] : (enter ? enter[c] : 0.0);
-            }
-            tr[e - ntab] = v;
-        }
-    }
-}
 
 // a DPP move of both halves of a double; CTRL permutes lanes within a row of 16, every lane has a source
 template <int CTRL>
@@ -321,9 +276,7 @@ extern "C" int dsp_dhmm_decode(const double *emit, const double *stay, const dou
     double2 *tr = (double2 *)((char *)workspace + pl.tab);
     int32_t *j0 = (int32_t *)((char *)workspace + pl.tab + pl.tr);
     const int NS = pl.NS;
-    const int64_t elems = (int64_t)K * NS * 64 + NS * 64 + 64;
-    hipLaunchKernelGGL(dsp::dhmm_decode_pack, dim3((unsigned)std::min<int64_t>((elems + 255) / 256, 1024)), dim3(256), 0, s, emit,
-                       stay, adv, n_states, enter, (int)C, Smax, K, NS, tab, tr, j0);
+    dsp::dhmm_decode_pack_launch(s, pl, workspace, emit, stay, adv, n_states, enter, (int)C, Smax, K);
     const int G = (int)std::min<int64_t>(N, dsp::DHMM_DECODE_WAVES);
     const size_t lds = dsp::decode_lds_bytes(T, NS);
     dsp::dhmm_with_slots(NS, [&](auto ns) {

@@ -1,10 +1,12 @@
 // hmm_internal.h -- what the left-to-right HMM files share: hmm.hip (Gaussian), dhmm.hip (discrete, Viterbi),
-// dhmm_fb.hip (discrete, forward-backward) and dhmm_decode.hip (connected words).
+// dhmm_fb.hip (discrete, forward-backward), dhmm_decode.hip (connected words) and dhmm_force.hip (forced alignment).
 //   bounds         of a model set and of a launch, and the discrete plan's dhmm_in_plan
 //   seg rows       hmm_walk_back (the lane's path from the direction words), hmm_seg_ok (a given row's check)
 //   the record     of a discrete model: dhmm_record / dhmm_pitch / dhmm_tr_offset / dhmm_lds_bytes, dhmm_pack
 //                  (the set into the workspace), dhmm_stage (one record into LDS), dhmm_lds_limit
 //   dhmm_with_slots    the 8 / 16 / 32 register-slot dispatch of a launch
+//   the set by model   dhmm_decode_pack with its plan and launch: the layout a wave reads whose lanes are models
+//                  (dhmm_decode.hip) or transcript positions (dhmm_force.hip)
 // Kernels are static, as in csr_pairs.h: every object that launches one has its own copy.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -136,6 +138,69 @@ static inline hipError_t dhmm_lds_limit(Kernel kernel, size_t lds)
 {
     if (lds <= 65536) return hipSuccess;
     return hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+}
+
+// ---- the set for a wave whose lanes read it by model (dhmm_decode.hip: a lane per model; dhmm_force.hip: a
+// lane per transcript position, reading its word's column) ----
+// tab [K][NS][64] doubles, END-aligned like the record above (state s of a model of S states in slot s + NS - S,
+// so every model's exit is slot NS - 1); the slots before a model's first state, a model with an invalid
+// n_states and the columns c >= C hold +inf, so their cells start at +inf and stay there.  tr [NS][64] pairs
+// (stay, cost of coming in from the slot before): adv[s-1], and at the model's first slot enter[c] (NULL: 0.0).
+// j0 [64]: that first slot, NS where the model is never entered.
+struct DecodePlan {
+    int NS;
+    size_t tab, tr, j0;  // bytes of the three parts
+    size_t total() const { return tab + tr + j0; }
+};
+static inline DecodePlan decode_plan(int Smax, int K)
+{
+    DecodePlan pl;
+    pl.NS = dhmm_slots(Smax);
+    pl.tab = up256((size_t)K * pl.NS * 64 * 8);
+    pl.tr = up256((size_t)pl.NS * 64 * 16);
+    pl.j0 = up256(64 * 4);
+    return pl;
+}
+
+static __global__ __launch_bounds__(256) void dhmm_decode_pack(const double *__restrict__ emit, const double *__restrict__ stay,
+                                                               const double *__restrict__ adv, const int32_t *__restrict__ n_states,
+                                                               const double *__restrict__ enter, int C, int Smax, int K, int NS,
+                                                               double *__restrict__ tab, double2 *__restrict__ tr,
+                                                               int32_t *__restrict__ j0)
+{
+    const int ntab = K * NS * 64, ntr = NS * 64;
+    for (int e = (int)blockIdx.x * 256 + (int)threadIdx.x; e < ntab + ntr + 64; e += (int)gridDim.x * 256) {
+        const int c = e % 64;
+        const int S = c < C ? n_states[c] : 0;
+        const bool ok = S >= 1 && S <= Smax;
+        if (e >= ntab + ntr) {
+            j0[c] = ok ? NS - S : NS;
+            continue;
+        }
+        const int j = (e / 64) % NS, s = ok ? j - (NS - S) : -1;
+        const bool in = s >= 0;
+        const int64_t cs = (int64_t)c * Smax + s;
+        if (e < ntab) {
+            tab[e] = in ? emit[cs * K + e / (NS * 64)] : (double)INFINITY;
+        } else {
+            double2 v = make_double2(0.0, 0.0);
+            if (in) {
+                v.x = stay[cs];
+                v.y = s > 0 ? adv[cs - 1] : (enter ? enter[c] : 0.0);
+            }
+            tr[e - ntab] = v;
+        }
+    }
+}
+// the pack's launch on stream s into the plan's three parts at ws
+static inline void dhmm_decode_pack_launch(hipStream_t s, const DecodePlan &pl, void *ws, const double *emit, const double *stay,
+                                           const double *adv, const int32_t *n_states, const double *enter, int C, int Smax,
+                                           int K)
+{
+    const int64_t elems = (int64_t)K * pl.NS * 64 + pl.NS * 64 + 64;
+    hipLaunchKernelGGL(dhmm_decode_pack, dim3((unsigned)((elems + 255) / 256 < 1024 ? (elems + 255) / 256 : 1024)), dim3(256), 0, s,
+                       emit, stay, adv, n_states, enter, C, Smax, K, pl.NS, (double *)ws, (double2 *)((char *)ws + pl.tab),
+                       (int32_t *)((char *)ws + pl.tab + pl.tr));
 }
 
 }  // namespace dsp

@@ -43,6 +43,7 @@ EXPORTS = ("dsp_extract_lds_bytes", "dsp_extract_fast_layout", "dsp_extract_feat
            "dsp_vq_workspace_bytes", "dsp_vq_score", "dsp_vq_assign", "dsp_vq_accumulate",
            "dsp_dhmm_workspace_bytes", "dsp_dhmm_score", "dsp_dhmm_align", "dsp_dhmm_accumulate",
            "dsp_dhmm_decode_workspace_bytes", "dsp_dhmm_decode",
+           "dsp_dhmm_force_workspace_bytes", "dsp_dhmm_force_align", "dsp_dhmm_force_accumulate",
            "dsp_dhmm_fb_workspace_bytes", "dsp_dhmm_forward", "dsp_dhmm_expect",
            "dsp_pitch_workspace_bytes", "dsp_pitch_track", "dsp_lpc_workspace_bytes", "dsp_lpc_autocorr",
            "dsp_lpc_solve")
@@ -199,6 +200,13 @@ def load_library(path=LIB_PATH):
         L.dsp_dhmm_decode_workspace_bytes.argtypes = [i64, i64, i32, i32, i32]
         L.dsp_dhmm_decode.restype = i32  # emit, stay, adv, n_states, enter, C, Smax, K, sym, len, N, T, max_words, outputs
         L.dsp_dhmm_decode.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, vp, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]
+    if hasattr(L, "dsp_dhmm_force_align"):  # (older A/B variants lack forced alignment and embedded training)
+        L.dsp_dhmm_force_workspace_bytes.restype = sz
+        L.dsp_dhmm_force_workspace_bytes.argtypes = [i64, i64, i32, i32, i32, i32]
+        L.dsp_dhmm_force_align.restype = i32  # the decoder's model arguments, sym, len, N, T, trans, n_trans, Wmax, score, seg
+        L.dsp_dhmm_force_align.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, vp, vp, i64, i32, vp, vp, i32, vp, vp, vp, sz, vp]
+        L.dsp_dhmm_force_accumulate.restype = i32  # ..., seg, cnt_emit, cnt, n_valid, valid, ws
+        L.dsp_dhmm_force_accumulate.argtypes = [vp, i64, i32, i32, vp, vp, i64, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, sz, vp]
     if hasattr(L, "dsp_dhmm_forward"):  # (older A/B variants lack forward scoring and the expected counts)
         model = [vp, vp, vp, vp, i64, i32, i32]  # pemit, pstay, padv, n_states, C, Smax, K
         syms = [vp, vp, i64, i32]  # sym, len, N, T

@@ -578,6 +578,9 @@ class DiscreteHmmClassifier(SequenceClassifier):
     prob_.to_costs() and totals_ to the per-class sums of ``dhmm_nll`` over the members with a non-zero
     likelihood, added in list order on the host; after Viterbi training prob_ is built from the same counts as
     model_ round by round by ``DhmmProbSet``'s formulas (``prev=`` included), so it holds the same models.
+    ``fit_connected`` trains the same models from connected utterances and their transcripts instead of
+    isolated clips, and ``align`` places a known word sequence in an utterance (csrc/dhmm_force.hip, DESIGN.md
+    §4.18); after ``fit_connected`` totals_ is float64 [rounds run].
     No CPU path: ``fit`` and ``predict`` raise HipError without a HIP device (constructing needs none).
     """
 
@@ -695,16 +698,121 @@ class DiscreteHmmClassifier(SequenceClassifier):
         Returns (labels, starts): per utterance the class labels of its words in time order and their first
         frames, both empty for an utterance no word sequence fits."""
         from .pipeline import dhmm_decode
-        Xq, nq = _as_padded(X, lengths)
-        if Xq.shape[2] != self.tokenizer_.codebook_.shape[1]:
-            raise ValueError("X has %d feature channels, the fitted codebook %d"
-                             % (Xq.shape[2], self.tokenizer_.codebook_.shape[1]))
+        Xq, nq = self._symbols(X, lengths)
         sym = self.tokenizer_.transform(self._scale(Xq, nq), nq)
         _, n_words, words, start, _ = dhmm_decode(self.model_, sym, nq, enter=word_penalty, max_words=max_words)
         n_words, words, start = (t.cpu().numpy() for t in (n_words, words, start))
         kept = np.minimum(n_words, words.shape[1])
         return ([self.classes_[words[i, :kept[i]]] for i in range(len(kept))],
                 [start[i, :kept[i]].copy() for i in range(len(kept))])
+
+    def _transcript_codes(self, transcripts, N):
+        """The transcripts' labels as indices into ``classes_``: (trans int32 [N, Wmax], n_trans int32 [N])."""
+        from .pipeline import _dhmm_transcripts
+        if len(transcripts) != N:
+            raise ValueError("%d transcripts for %d utterances" % (len(transcripts), N))
+        rows = []
+        for r in transcripts:
+            r = np.asarray(r).reshape(-1)
+            at = np.searchsorted(self.classes_, r) if len(r) else np.zeros(0, np.int64)
+            at = np.minimum(at, len(self.classes_) - 1)
+            if len(r) and (self.classes_[at] != r).any():
+                raise ValueError("transcript label %r is not one of the fitted classes" % (r[self.classes_[at] != r][0],))
+            rows.append(at)
+        return _dhmm_transcripts(rows, None, N)
+
+    def _symbols(self, X, lengths):
+        """The padded utterances of ``decode`` and ``align``, checked against the fitted codebook's channels."""
+        Xq, nq = _as_padded(X, lengths)
+        if Xq.shape[2] != self.tokenizer_.codebook_.shape[1]:
+            raise ValueError("X has %d feature channels, the fitted codebook %d"
+                             % (Xq.shape[2], self.tokenizer_.codebook_.shape[1]))
+        return Xq, nq
+
+    def align(self, X, transcripts, lengths=None, word_penalty=0.0):
+        """Forced alignment: where are the words of each utterance's KNOWN word sequence?  Every utterance is
+        aligned against the concatenation of its transcript's class models (csrc/dhmm_force.hip,
+        dsp_dhmm_force_align; at most ``pipeline.DHMM_FORCE_MAX_WORDS`` words a transcript).
+        The frames are tokenised exactly as ``decode`` does; ``word_penalty`` is ``decode``'s.  ``transcripts``:
+        per utterance the sequence of its words' class labels; a label not in ``classes_`` raises ValueError.
+        Returns (starts, scores): per utterance the first frame of each transcript word, and the forced score
+        float64 [n]; an utterance the transcript does not fit gets empty starts and a score of +inf."""
+        from .pipeline import dhmm_force_align
+        Xq, nq = self._symbols(X, lengths)
+        trans, n_trans = self._transcript_codes(transcripts, len(nq))
+        sym = self.tokenizer_.transform(self._scale(Xq, nq), nq)
+        score, seg = dhmm_force_align(self.model_, sym, nq, trans, enter=word_penalty, n_trans=n_trans)
+        score, first = score.cpu().numpy(), seg[:, :, 0].cpu().numpy()
+        return [first[i, :n_trans[i]].copy() if score[i] < np.inf else np.zeros(0, np.int32) for i in range(len(nq))], score
+
+    def fit_connected(self, X, transcripts, lengths=None, word_penalty=0.0):
+        """Embedded Viterbi training from connected utterances and their transcripts -- no word boundary is
+        marked by hand (csrc/dhmm_force.hip).  ``classes_`` becomes the sorted labels of all
+        transcripts (at most ``pipeline.DHMM_DECODE_MAX_MODELS``); normalisation and the tokeniser are fitted on
+        all utterance frames; the flat start (``pipeline.dhmm_flat_segmentation``) and one accumulate give the
+        first models; then up to ``n_iter`` rounds of align -> accumulate -> rebuild
+        (``DhmmModelSet(..., prev=model)``), stopping early when a round changes no entry of seg.  An utterance
+        shorter than its chain of states is left out; a word with no instance in any utterance that is long
+        enough raises ValueError, as does training='baum_welch' (there is no embedded forward-backward).
+        After the fit: tokenizer_, model_, n_iter_, totals_ float64 [rounds]: per round the forced scores of the
+        valid utterances added in utterance order on the host; with scoring='forward' also prob_, built from the
+        same counts as in ``fit``."""
+        from .pipeline import (DHMM_DECODE_MAX_MODELS, DhmmForceUpdater, DhmmModelSet, DhmmProbSet, VqTokenizer,
+                               dhmm_flat_segmentation)
+        if self.training == 'baum_welch':
+            raise ValueError("fit_connected trains by Viterbi re-estimation: there is no embedded Baum-Welch")
+        X, n = _as_padded(X, lengths)
+        if len(transcripts) != len(X):
+            raise ValueError("%d transcripts for %d utterances" % (len(transcripts), len(X)))
+        words = [np.asarray(r).reshape(-1) for r in transcripts]
+        if any(len(r) < 1 for r in words):
+            raise ValueError("empty transcript at index %d" % [len(r) < 1 for r in words].index(True))
+        self.classes_ = np.unique(np.concatenate(words))
+        C, K = len(self.classes_), self.n_codes
+        if C > DHMM_DECODE_MAX_MODELS:
+            raise ValueError("fit_connected takes at most %d word classes, got %d" % (DHMM_DECODE_MAX_MODELS, C))
+        states = np.full(C, self.n_states, np.int32) if np.ndim(self.n_states) == 0 else self.n_states
+        if len(states) != C:
+            raise ValueError("%d n_states for %d classes" % (len(states), C))
+        trans, n_trans = self._transcript_codes(words, len(X))
+        Smax = int(states.max())
+        if self.normalize:
+            frames = X[np.arange(X.shape[1])[None, :] < n[:, None]]  # all valid frames, as _training_set
+            self.mean_ = np.mean(frames, axis=0)
+            std = np.std(frames, axis=0)
+            self.std_ = np.where(std == 0, 1.0, std)
+        X = self._scale(X, n)
+        self.tokenizer_ = VqTokenizer(K, self.vq_iter, self.eps).fit(X, n)
+        updater = DhmmForceUpdater(self.tokenizer_.transform(X, n), n, trans, n_trans)
+        seg = dhmm_flat_segmentation(n, trans, n_trans, states, Smax)
+        stats = updater.accumulate(states, K, seg)
+        n_valid = stats[2].cpu().numpy()
+        if (n_valid == 0).any():
+            c = int(np.argmin(n_valid))
+            raise ValueError("class %r has no instance in an utterance of at least as many frames as its transcript "
+                             "has states" % (self.classes_[c],))
+        model = DhmmModelSet(*stats[:3], states, self.alpha, self.trans_floor)
+        forward = self.scoring == 'forward'  # then prob_ follows model_ round by round, prev= included
+        prob = DhmmProbSet(stats[0], stats[2], states, self.alpha, self.trans_floor) if forward else None
+        totals = []
+        for _ in range(self.n_iter):
+            score, new_seg = updater.align(model, word_penalty)
+            stats = updater.accumulate(states, K, new_seg)
+            kept = score.cpu().numpy()[stats[3].cpu().numpy() != 0]
+            totals.append(np.cumsum(kept)[-1] if len(kept) else 0.0)  # sequential, utterance order: np.sum adds pairwise
+            model = DhmmModelSet(*stats[:3], states, self.alpha, self.trans_floor, prev=model)
+            if forward:
+                prob = DhmmProbSet(stats[0], stats[2], states, self.alpha, self.trans_floor, prev=prob)
+            new_seg = new_seg.cpu().numpy()
+            same = np.array_equal(new_seg, seg)
+            seg = new_seg
+            if same:
+                break
+        self.model_, self.n_iter_, self.totals_ = model, len(totals), np.array(totals, dtype=np.float64)
+        if forward:
+            self.prob_ = prob
+        self._index = None
+        return self
 
 
 def word_error_rate(ref, hyp):

@@ -1156,12 +1156,7 @@ def dhmm_decode(models, sym, lengths, enter=None, max_words=None):
     max_words = T if max_words is None else int(max_words)
     if not 1 <= max_words <= T:
         raise ValueError("max_words must lie in [1, T = %d]" % T)
-    cost = None
-    if enter is not None:
-        cost = np.array(np.broadcast_to(np.asarray(_as_host(enter), np.float64), (C,)))
-        if np.isnan(cost).any() or (cost == -np.inf).any():
-            raise ValueError("enter must be finite or +inf")
-        cost = _as_device(cost, torch.float64, d)
+    cost = _dhmm_enter(enter, C, d)
     score = torch.empty(N, dtype=torch.float64, device=d)
     n_words = torch.empty(N, dtype=torch.int32, device=d)
     words = torch.empty((N, max_words), dtype=torch.int32, device=d)
@@ -1174,6 +1169,147 @@ def dhmm_decode(models, sym, lengths, enter=None, max_words=None):
                                         _hip.ptr(ws), ws.numel(), _hip.stream_handle(d))
         _hip.check(rc, "dsp_dhmm_decode")
     return score, n_words, words, start, cum
+
+
+DHMM_FORCE_MAX_WORDS = 64  # words of one transcript at most (csrc/dhmm_force.hip: a lane per transcript position)
+
+
+def _dhmm_transcripts(transcripts, n_trans, N):
+    """(trans int32 [N, Wmax], n_trans int32 [N]) on the host from a list of index sequences, or from a padded
+    [N, Wmax] array with its word counts; 1 <= Wmax <= ``DHMM_FORCE_MAX_WORDS``."""
+    if n_trans is None:
+        rows = [np.asarray(_as_host(r)).astype(np.int64).reshape(-1) for r in transcripts]
+        n_trans = np.array([len(r) for r in rows], np.int32)
+        trans = np.full((len(rows), max(1, int(n_trans.max()) if len(rows) else 1)), -1, np.int32)
+        for i, r in enumerate(rows):
+            trans[i, :len(r)] = r
+    else:
+        trans = np.ascontiguousarray(_as_host(transcripts).astype(np.int32))
+        n_trans = _as_host(n_trans).astype(np.int32).reshape(-1)
+        if trans.ndim != 2:
+            raise ValueError("padded transcripts must be [N, Wmax], got shape %s" % (trans.shape,))
+    if trans.shape[0] != N or len(n_trans) != N:
+        raise ValueError("%d transcripts and %d word counts for %d utterances" % (trans.shape[0], len(n_trans), N))
+    if not 1 <= trans.shape[1] <= DHMM_FORCE_MAX_WORDS:
+        raise ValueError("a transcript holds 1 .. %d words, got Wmax = %d" % (DHMM_FORCE_MAX_WORDS, trans.shape[1]))
+    return trans, n_trans
+
+
+def _dhmm_enter(enter, C, device):
+    """The entry costs of ``dhmm_decode`` and ``dhmm_force_align`` on the device, or None (all 0.0)."""
+    import torch
+    if enter is None:
+        return None
+    cost = np.array(np.broadcast_to(np.asarray(_as_host(enter), np.float64), (C,)))
+    if np.isnan(cost).any() or (cost == -np.inf).any():
+        raise ValueError("enter must be finite or +inf")
+    return _as_device(cost, torch.float64, device)
+
+
+def dhmm_flat_segmentation(lengths, trans, n_trans, n_states, Smax):
+    """The flat start of embedded training (host only): an utterance of n frames against the chain of its
+    transcript's J = S_0 + S_1 + ... concatenated states; chain state j begins at frame floor(j n / J) --
+    ``hmm_uniform_segmentation``'s rule on the chain.  Returns seg int32 [N, Wmax, Smax]: -1 behind each word's
+    states and behind the transcript, and everywhere when n < J or the transcript is invalid (a word count
+    outside 1 .. Wmax, an index outside the set, a model with n_states outside 1 .. Smax)."""
+    n = np.asarray(lengths).astype(np.int64).reshape(-1)
+    S_all = np.asarray(n_states).astype(np.int64).reshape(-1)
+    trans, L = _dhmm_transcripts(trans, n_trans, len(n))
+    trans, L = trans.astype(np.int64), L.astype(np.int64)
+    N, Wmax = trans.shape
+    Smax = int(Smax)
+    inside = np.arange(Wmax)[None, :] < L[:, None]
+    wok = (trans >= 0) & (trans < len(S_all))
+    S = np.where(inside & wok, S_all[np.where(wok, trans, 0)], 0)  # [N, Wmax], 0 behind the transcript
+    ok = (L >= 1) & (L <= Wmax) & ~(inside & (~wok | (S < 1) | (S > Smax))).any(axis=1)
+    S = np.where(ok[:, None], np.minimum(S, Smax), 0)
+    J = S.sum(axis=1)
+    ok &= n >= J
+    j = (np.cumsum(S, axis=1) - S)[:, :, None] + np.arange(Smax)[None, None, :]  # the chain index of (i, s)
+    seg = (j * n[:, None, None]) // np.maximum(J, 1)[:, None, None]
+    keep = ok[:, None, None] & (np.arange(Smax)[None, None, :] < S[:, :, None])
+    return np.where(keep, seg, -1).astype(np.int32)
+
+
+class DhmmForceUpdater:
+    """The symbol rows of an embedded training run uploaded once with their transcripts (trans [N, Wmax],
+    n_trans [N], or a list of index sequences with ``n_trans=None``); one workspace that only grows is held
+    across the rounds.  ``align`` is one ``dsp_dhmm_force_align`` call, ``accumulate`` one
+    ``dsp_dhmm_force_accumulate`` call (include/dsp_audiorec.h, csrc/dhmm_force.hip)."""
+
+    def __init__(self, sym, lengths, trans, n_trans=None):
+        import torch
+        self.device = d = _hip.require_device()
+        self.seqs, self.len_s = _dhmm_operand(sym, lengths, d)
+        self.N, self.T = self.seqs.shape
+        trans, n_trans = _dhmm_transcripts(trans, n_trans, self.N)
+        self.Wmax = trans.shape[1]
+        self.trans, self.n_trans = _as_device(trans, torch.int32, d), _as_device(n_trans, torch.int32, d)
+        self._ws = None
+
+    def _workspace(self, C, Smax, K):
+        nbytes = _hip.lib().dsp_dhmm_force_workspace_bytes(C, self.N, self.T, self.Wmax, Smax, K)
+        self._ws = _grown(self._ws, nbytes, _DHMM_FORCE_SHAPE, self.device)
+        return self._ws
+
+    def align(self, models, enter=None, with_seg=True):
+        """(score float64 [N], seg int32 [N, Wmax, Smax] or None) of every utterance against its transcript."""
+        import torch
+        d = self.device
+        margs = _dhmm_model_args(models, d)
+        C, Smax, K = margs[-3:]
+        cost = _dhmm_enter(enter, C, d)
+        score = torch.empty(self.N, dtype=torch.float64, device=d)
+        seg = torch.empty((self.N, self.Wmax, Smax), dtype=torch.int32, device=d) if with_seg else None
+        if self.N > 0:
+            ws = self._workspace(C, Smax, K)
+            rc = _hip.lib().dsp_dhmm_force_align(*margs[:4], _hip.ptr(cost), C, Smax, K, _hip.ptr(self.seqs),
+                                                 _hip.ptr(self.len_s), self.N, self.T, _hip.ptr(self.trans),
+                                                 _hip.ptr(self.n_trans), self.Wmax, _hip.ptr(score), _hip.ptr(seg),
+                                                 _hip.ptr(ws), ws.numel(), _hip.stream_handle(d))
+            _hip.check(rc, "dsp_dhmm_force_align")
+        return score, seg
+
+    def accumulate(self, n_states, K, seg):
+        """The embedded re-estimation from a given segmentation: (cnt_emit int32 [C, Smax, K], cnt int32
+        [C, Smax], n_valid int32 [C], valid int32 [N]) on the device."""
+        import torch
+        d = self.device
+        n_states, seg = _as_device(n_states, torch.int32, d).reshape(-1), _as_device(seg, torch.int32, d)
+        C, K = n_states.numel(), int(K)
+        if seg.dim() != 3 or seg.shape[0] != self.N or seg.shape[1] != self.Wmax:
+            raise ValueError("seg %s for %d utterances of %d words at most" % (tuple(seg.shape), self.N, self.Wmax))
+        Smax = seg.shape[2]
+        cnt_emit = torch.empty((C, Smax, K), dtype=torch.int32, device=d)  # zeroed by the call itself
+        cnt = torch.empty((C, Smax), dtype=torch.int32, device=d)
+        n_valid = torch.empty(C, dtype=torch.int32, device=d)
+        valid = torch.empty(self.N, dtype=torch.int32, device=d)
+        ws = self._workspace(C, Smax, K)
+        rc = _hip.lib().dsp_dhmm_force_accumulate(_hip.ptr(n_states), C, Smax, K, _hip.ptr(self.seqs), _hip.ptr(self.len_s),
+                                                  self.N, self.T, _hip.ptr(self.trans), _hip.ptr(self.n_trans), self.Wmax,
+                                                  _hip.ptr(seg.contiguous()), _hip.ptr(cnt_emit), _hip.ptr(cnt),
+                                                  _hip.ptr(n_valid), _hip.ptr(valid), _hip.ptr(ws), ws.numel(),
+                                                  _hip.stream_handle(d))
+        _hip.check(rc, "dsp_dhmm_force_accumulate")
+        return cnt_emit, cnt, n_valid, valid
+
+
+_DHMM_FORCE_SHAPE = ("unsupported forced-alignment shape (1 <= C <= %d, 1 <= Wmax <= %d, 1 <= T <= 1024, 1 <= Smax <= %d, "
+                     "1 <= K <= %d)" % (DHMM_DECODE_MAX_MODELS, DHMM_FORCE_MAX_WORDS, HMM_MAX_STATES, DHMM_MAX_SYMBOLS))
+
+
+def dhmm_force_align(models, sym, lengths, transcripts, enter=None, with_seg=True, n_trans=None):
+    """Forced alignment (include/dsp_audiorec.h: dsp_dhmm_force_align) of the symbol rows sym int32 [N, T]
+    against the concatenation of their transcripts' word models from the ``DhmmModelSet`` (at most
+    ``DHMM_DECODE_MAX_MODELS`` models, ``DHMM_FORCE_MAX_WORDS`` words a transcript).  ``transcripts``: a list of
+    model-index sequences, or a padded [N, Wmax] array with ``n_trans``.  ``enter`` as ``dhmm_decode``'s.
+    Returns (score float64 [N], seg int32 [N, Wmax, Smax] or None) on the device: seg[u, i, s] is the first
+    frame of state s of word i (-1 behind the word's states and behind the transcript, and everywhere for an
+    utterance whose score is +inf)."""
+    if not 1 <= models.shape[0] <= DHMM_DECODE_MAX_MODELS:
+        raise ValueError("forced alignment takes 1 .. %d word models, got %d" % (DHMM_DECODE_MAX_MODELS, models.shape[0]))
+    trans, n_trans = _dhmm_transcripts(transcripts, n_trans, len(lengths))
+    return DhmmForceUpdater(sym, lengths, trans, n_trans).align(models, enter, with_seg)
 
 
 class VqTokenizer:

@@ -36,7 +36,7 @@ extern "C" {
                               5: queue_ws is 4 KiB (each counter on its own 256-B line);
                               6: the extraction entry points take out_stride (packed result rows);
                                  dsp_knn_classify takes flags (DSP_KNN_REF_READY).
-                              Still 6 with the dsp_mlp_*, dsp_svc_*, dsp_gnb_*, dsp_tree_* and dsp_dtw_* (dsp_dtw_align, dsp_dtw_dba_update included) and dsp_hmm_* and dsp_vq_* and dsp_dhmm_* (dsp_dhmm_decode, dsp_dhmm_forward and dsp_dhmm_expect included) and dsp_pitch_* and dsp_lpc_* entry points: new symbols only, no
+                              Still 6 with the dsp_mlp_*, dsp_svc_*, dsp_gnb_*, dsp_tree_* and dsp_dtw_* (dsp_dtw_align, dsp_dtw_dba_update included) and dsp_hmm_* and dsp_vq_* and dsp_dhmm_* (dsp_dhmm_decode, dsp_dhmm_forward, dsp_dhmm_expect and dsp_dhmm_force_* included) and dsp_pitch_* and dsp_lpc_* entry points: new symbols only, no
                               existing signature or meaning changed, so callers built against 6 keep
                               working (a binding that needs them checks for the symbols) */
 
@@ -840,6 +840,72 @@ int dsp_dhmm_decode(const double *emit, const double *stay, const double *adv, c
                     const double *enter, int64_t C, int Smax, int K, const int32_t *sym, const int32_t *len, int64_t N,
                     int T, int max_words, double *score, int32_t *n_words, int32_t *words, int32_t *start, double *cum,
                     void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Forced alignment and embedded Viterbi re-estimation: an utterance of several words in a row with a KNOWN
+ * word sequence (its transcript) is aligned against the concatenation of the transcript's word models, and
+ * the models are re-estimated from those alignments -- training on the kind of data dsp_dhmm_decode decodes,
+ * with no word boundary marked by hand.  csrc/dhmm_force.hip, DESIGN.md §4.18.  Bit for bit like the entry
+ * points above: fp64 add and compare and integer counts only.
+ *
+ * Inputs.  The model set and enter float64 [C] exactly as for dsp_dhmm_decode, with the same value rules;
+ *   enter NULL means all 0.0.  1 <= C <= 64, Smax <= 32, K <= 256.  sym int32 [N, T], len int32 [N],
+ *   T <= 1024.  trans int32 [N, Wmax]: the model index of each word of utterance u's transcript, in time
+ *   order; n_trans int32 [N] its word count; 1 <= Wmax <= 64 (DSP_DHMM_FORCE_MAX_WORDS).  Entries of trans
+ *   behind n_trans[u] are never read through.
+ * Recurrence.  Utterance u of n frames with transcript w_0 .. w_{L-1}, S_i = n_states[w_i]; position i has
+ *   the states (i, 0 .. S_i - 1); V(-1, ., .) = +inf.  For t = 0 .. n-1:
+ *     e = emit[w_i, s, sym[t]]
+ *     a = V(t-1,i,s) + stay[w_i,s]
+ *     b = s > 0   ?  V(t-1,i,s-1) + adv[w_i,s-1]
+ *       : i > 0   ?  V(t-1,i-1,S_{i-1}-1) + enter[w_i]
+ *       : t == 0  ?  0.0 + enter[w_0]
+ *       :            +inf
+ *     advance iff b < a (strictly; ties stay)
+ *     V(t,i,s) = e + (advance ? b : a)
+ *     score = V(n-1, L-1, S_{L-1}-1)
+ *   This is dsp_dhmm_decode's cell with the word loop replaced by the transcript's chain; the decoder's
+ *   free exit is kept: adv[c, S-1] stays unread.
+ * Result.  score float64 [N].  seg int32 [N, Wmax, Smax]: the first frame of every state of every position,
+ *   an absolute frame index of the utterance, walked back from (n-1, L-1, last state) along the advance
+ *   decisions; -1 for s >= S_i and for i >= L.  seg[u, i, 0] is word i's first frame.
+ *   score is +inf and the whole seg row -1 when n < 1 or n > T; when L < 1 or L > Wmax; when some
+ *   trans[u, i], i < L, lies outside [0, C) or names a model whose n_states is outside 1 .. Smax; when some
+ *   sym[t], t < n, lies outside [0, K) (such a symbol never indexes a table); and when the recurrence leaves
+ *   +inf (n < sum S_i, a +inf enter, ...).  Either output may be NULL; without seg no direction bit is
+ *   stored and nothing is walked.
+ * dsp_dhmm_force_accumulate: the embedded Viterbi re-estimate from a GIVEN seg [N, Wmax, Smax], as
+ *   dsp_dhmm_accumulate is from its seg.  An utterance is valid when its length and its transcript are valid
+ *   as above, all its symbols are in range and its seg row is well formed: seg[0][0] = 0, strictly increasing
+ *   over the sum S_i concatenated states, the last one < n, and -1 exactly where the definition says.  Any
+ *   other utterance is skipped whole, with valid[u] = 0.
+ *     cnt_emit int32 [C, Smax, K]  frames of valid utterances that sit in state s of an instance of word c
+ *                                  and carry symbol k
+ *     cnt      int32 [C, Smax]     frames of valid utterances in state s of an instance of word c
+ *     n_valid  int32 [C]           word instances of c in valid utterances: every instance leaves each of its
+ *                                  states once, so p_stay = (cnt - n_valid) / cnt as for dsp_dhmm_accumulate
+ *     valid    int32 [N]           1 for a valid utterance, 0 for a skipped one
+ *   Rows s >= S are zero, as is a model with no instance.  All counts are integers, gathered with integer
+ *   atomics in any order and still defined exactly; the call zeroes them itself.  No floating-point total is
+ *   formed on the device: the training objective is the caller's, from dsp_dhmm_force_align's scores.
+ * workspace  device scratch of dsp_dhmm_force_workspace_bytes(C, N, T, Wmax, Smax, K) bytes (0: sizes outside
+ *   the plan) for either call: dsp_dhmm_decode's transposed set and one 32-bit direction word per frame and
+ *   lane of every resident wave.  Nothing in it is carried from one call to the next.
+ * Both calls check their host arguments before any launch (DSP_ERR_ARGS, DSP_ERR_WORKSPACE), return DSP_OK
+ * with nothing to do (dsp_dhmm_force_align: N = 0 or both outputs NULL; dsp_dhmm_force_accumulate with N = 0
+ * zeroes the counts), make no host synchronisation and no allocation, and write only to their outputs and the
+ * workspace, on the caller's stream.
+ */
+#define DSP_DHMM_FORCE_MAX_WORDS 64
+size_t dsp_dhmm_force_workspace_bytes(int64_t C, int64_t N, int T, int Wmax, int Smax, int K);
+int dsp_dhmm_force_align(const double *emit, const double *stay, const double *adv, const int32_t *n_states,
+                         const double *enter, int64_t C, int Smax, int K, const int32_t *sym, const int32_t *len, int64_t N,
+                         int T, const int32_t *trans, const int32_t *n_trans, int Wmax, double *score, int32_t *seg,
+                         void *workspace, size_t workspace_bytes, void *stream);
+int dsp_dhmm_force_accumulate(const int32_t *n_states, int64_t C, int Smax, int K, const int32_t *sym, const int32_t *len,
+                              int64_t N, int T, const int32_t *trans, const int32_t *n_trans, int Wmax, const int32_t *seg,
+                              int32_t *cnt_emit, int32_t *cnt, int32_t *n_valid, int32_t *valid, void *workspace,
+                              size_t workspace_bytes, void *stream);
 
 /*
  * Short-time autocorrelation pitch track -- the fourth classical time-domain feature next to energy,
