@@ -38,9 +38,9 @@ static constexpr int GF_C = 16;      // columns per workgroup
 static constexpr int GF_S = GF_CONS / GF_C;  // class slots per workgroup; slot C is "all rows"
 
 // One tile of one chain: rows [0, rows) of column cp (stride GF_C) with their labels lp, added in
-// row order.  PASS 0 adds x and counts the chain's rows, PASS 1 adds (x - m)^2.  -0.0 + x is x for
-// every x (also for x = -0.0), so the addend of a row of another class is -0.0: the select is on the
-// addend, off the chain.  `any` (the all-rows slot) takes every row.
+// row order.  PASS 0 adds x and counts the chain's rows, PASS 1 adds (x - m)^2.  acc + -0.0 is acc for
+// every acc (also for acc = +-0.0), so the addend of a row of another class is -0.0: the select is on
+// the addend, off the chain.  `any` (the all-rows slot) takes every row.
 template <int PASS>
 __device__ __forceinline__ void gnb_fit_tile(const double *cp, const int32_t *lp, int rows, int slot, bool any,
                                              double m, double &acc, int &n)
@@ -104,12 +104,13 @@ __global__ __launch_bounds__(GF_T) void gnb_fit_kernel(const double *X, const in
         for (int u = 0; u < LPT; u++) tile[buf][(r0 + u * RPS) * GF_C + c] = v[u];
         lab[buf][l] = lv;
     };
-    // the chain starts from -0.0, which is numpy's start from the first row (-0.0 + x is x)
-    double m = 0.0, acc = -0.0;
+    // the chain starts from +0.0, np.add.reduce's own start (it adds the rows to its identity: a class whose
+    // rows are all -0.0 in a column has the mean +0.0, every other sum is the same from +0.0 and from -0.0)
+    double m = 0.0, acc = 0.0;
     int64_t cnt = 0;
     const bool all = slot == C;
     for (int pass = 0; pass < 2; pass++) {
-        acc = -0.0;
+        acc = 0.0;
         if (!consumer) load(0, 0);
         __syncthreads();
         for (int64_t t = 0; t < ntile; t++) {
@@ -270,6 +271,11 @@ __global__ __launch_bounds__(GNB_T) void gnb_predict_kernel(const GnbArgs a)
     if (!cert) atomicAdd(a.uncertified, 1);
 }
 
+// the uncertified count starts at 0 by a kernel's store, not a memset node (as svc_prep's, svm.hip):
+// a captured call is a plain chain of kernels.  gnb_predict_kernel has no kernel before it and its
+// workgroups are not ordered among themselves, so the store is a launch of its own
+__global__ void gnb_clear(int32_t *uncertified) { uncertified[0] = 0; }
+
 }  // namespace dsp
 
 namespace {
@@ -318,10 +324,10 @@ extern "C" int dsp_gnb_predict(const double *theta, const double *var, const dou
     if (!workspace || workspace_bytes < dsp_gnb_workspace_bytes(Nq, D, C)) return DSP_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     char *ws = (char *)workspace;
-    if (hipMemsetAsync(ws, 0, GNB_HEAD, s) != hipSuccess) return DSP_ERR_HIP;
-    if (Nq == 0) return DSP_OK;
     const int64_t blocks = (Nq + dsp::GNB_T - 1) / dsp::GNB_T;
     if (blocks > 0x7fffffff) return DSP_ERR_ARGS;
+    hipLaunchKernelGGL(dsp::gnb_clear, dim3(1), dim3(1), 0, s, (int32_t *)ws);
+    if (Nq == 0) return hipGetLastError() == hipSuccess ? DSP_OK : DSP_ERR_HIP;
     dsp::GnbArgs a;
     a.theta = theta, a.var = var, a.log_prior = log_prior, a.nconst = nconst, a.X = X;
     a.Nq = Nq, a.D = D, a.C = C;

@@ -45,9 +45,12 @@ __device__ __forceinline__ float float_below(double t)
 
 __global__ __launch_bounds__(256) void tree_pack(const int32_t *left, const int32_t *right, const int32_t *feature,
                                                  const double *threshold, const int32_t *leaf_class, int n_nodes,
-                                                 int4 *nodes)
+                                                 int4 *nodes, int32_t *unanswered)
 {
     const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+    // the walk's count starts at 0 by this kernel's store, not a memset node (as svc_prep's, svm.hip): a
+    // captured call is a plain chain of kernels
+    if (i == 0) unanswered[0] = 0;
     if (i >= n_nodes) return;
     const int l = left[i];
     int4 n;
@@ -117,14 +120,14 @@ extern "C" int dsp_tree_predict(const int32_t *children_left, const int32_t *chi
     if (!workspace || workspace_bytes < dsp_tree_workspace_bytes(n_nodes)) return DSP_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     char *ws = (char *)workspace;
-    if (hipMemsetAsync(ws, 0, dsp::TREE_HEAD, s) != hipSuccess) return DSP_ERR_HIP;
-    if (Nq == 0) return DSP_OK;
     const int64_t blocks = (Nq + dsp::TREE_T - 1) / dsp::TREE_T;
     if (blocks > 0x7fffffff) return DSP_ERR_ARGS;
     const int n = (int)n_nodes;
     int4 *nodes = (int4 *)(ws + dsp::TREE_HEAD);
+    // (also for Nq = 0: the count is tree_pack's to clear)
     hipLaunchKernelGGL(dsp::tree_pack, dim3((unsigned)((n_nodes + 255) / 256)), dim3(256), 0, s, children_left,
-                       children_right, feature, threshold, leaf_class, n, nodes);
+                       children_right, feature, threshold, leaf_class, n, nodes, (int32_t *)ws);
+    if (Nq == 0) return hipGetLastError() == hipSuccess ? DSP_OK : DSP_ERR_HIP;
     const dim3 grid((unsigned)blocks), block(dsp::TREE_T);
     if (n <= dsp::TREE_LDS_NODES)
         hipLaunchKernelGGL(dsp::tree_walk<true>, grid, block, (size_t)n * 16, s, nodes, n, D, max_depth, X, Nq, pred,

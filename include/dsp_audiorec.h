@@ -343,11 +343,13 @@ int dsp_svc_predict(const double *sv, const int32_t *n_support, const double *du
  *   epsilon      float64 [1]     epsilon_ = var_smoothing * the largest all-rows column variance
  *                                (np.var(X, axis=0).max(), the same two passes over all rows)
  *   These are numpy's own sequential fp64 chains (axis 0, D >= 2), neither reordered nor atomic:
- *   the four arrays equal GaussianNB().fit's bit for bit.  class_prior_ is class_count /
+ *   the four arrays equal GaussianNB().fit's bit for bit.  A chain starts from +0.0, np.add.reduce's
+ *   own start: a class whose rows are all -0.0 in a column has the mean +0.0 there, not -0.0.  class_prior_ is class_count /
  *   class_count.sum(), the caller's.
  *   workspace    device scratch of at least 8 D bytes.
  *   A class without rows gets class_count 0 and NaN in its theta and var rows (0 / 0); a row whose
- *   code is outside [0, C) counts for epsilon only.
+ *   code is outside [0, C) counts for epsilon only.  A NaN or an inf in a column makes that column's
+ *   var NaN, and -- as np.var(X, axis=0).max() does -- epsilon and with it every var NaN.
  *   Requires 2 <= D <= 4096 (D = 1: DSP_ERR_ARGS -- numpy sums that case pairwise), 1 <= C <= 64,
  *   N >= 1.
  *
@@ -365,8 +367,16 @@ int dsp_svc_predict(const double *sv, const int32_t *n_support, const double *du
  *            scikit-learn's; 0: the caller answers that row with scikit-learn itself (a row with a
  *            NaN or an infinity is never certified).  Equal inputs give equal bits, and a row's bits
  *            do not depend on Nq or on the row's position.
+ *            A score that is not finite -- Q_c overflows (a finite x whose (x - theta)^2 or quotient
+ *            overflows included), log_prior[c] = -inf, a class with NaN parameters -- leaves the whole
+ *            row uncertified, whichever class leads.  pred is taken with ">" from class 0 on: equal
+ *            scores (duplicate classes) give the first index and no certificate, and a NaN score
+ *            never replaces a leader (pred is then the caller's to redo, as for every uncertified row).
+ *            C = 1 is certified whenever its score is finite.
  * workspace  device scratch of dsp_gnb_workspace_bytes(Nq, D, C) bytes (0: sizes outside the plan);
- *            its first int32 is left holding the number of uncertified rows.
+ *            its first int32 is left holding the number of uncertified rows (0 for Nq = 0).  The
+ *            count is cleared by a kernel's store, so the call is a plain chain of kernels on
+ *            `stream` and may be captured in a graph and replayed: every replay recounts.
  * Requires 1 <= D <= 4096 (D <= 32: the query in registers), 1 <= C <= 64.
  */
 int dsp_gnb_fit(const double *X, const int32_t *y, int64_t N, int D, int C, double var_smoothing,
@@ -393,8 +403,15 @@ int dsp_gnb_predict(const double *theta, const double *var, const double *log_pr
  * it).  The walk ends on any
  * table: at most max_depth + 1 nodes are visited, and a child index outside (node, n_nodes) or a
  * feature index outside [0, D) ends it with pred = leaf = -1.
+ * A threshold is compared as a double: one outside the float32 range or between two float32
+ * subnormals decides as written (float32 subnormals are not flushed; x = -0.0 <= +0.0 and
+ * +0.0 <= -0.0 go left).  A NaN threshold compares false with every value: the walk goes right.  A
+ * double that rounds to +-inf as float32 -- the midpoint between FLT_MAX and 2^128 rounds to even,
+ * which is inf -- is not finite as float32.
  * workspace  device scratch of dsp_tree_workspace_bytes(n_nodes) bytes (the packed 16-byte nodes);
- *            its first int32 is left holding the number of rows answered -1.
+ *            its first int32 is left holding the number of rows answered -1 (0 for Nq = 0).  The
+ *            count is cleared by a kernel's store (as dsp_gnb_predict's): the call may be captured
+ *            in a graph and replayed.
  * dsp_tree_lds_nodes (host only): up to this many nodes the walk reads the table from LDS, beyond
  *            it from memory.
  * Requires 1 <= n_nodes < 2^31, max_depth >= 0, 1 <= D <= 4096.

@@ -12,8 +12,9 @@ SAFETY = 4.0  # the certificate's factor (the SVC's)
 
 # ---- fit ---------------------------------------------------------------------------------------
 def seq_sum(A):
-    """Column sums added in row order (np.cumsum never sums pairwise)."""
-    return np.cumsum(A, axis=0)[-1]
+    """Column sums added in row order (np.cumsum never sums pairwise) to +0.0, np.add.reduce's start: a
+    column of -0.0 alone sums to +0.0."""
+    return np.cumsum(A, axis=0)[-1] + 0.0
 
 
 def seq_mean_var(A):
@@ -24,7 +25,8 @@ def seq_mean_var(A):
 
 
 def gnb_fit(X, codes, C, var_smoothing=1e-9):
-    """(theta, var with epsilon, class_count int64, epsilon): every sum one sequential fp64 chain."""
+    """(theta, var with epsilon, class_count int64, epsilon): every sum one sequential fp64 chain.  A class
+    without rows has count 0 and NaN in its theta and var rows (0 / 0, include/dsp_audiorec.h)."""
     X = np.asarray(X, dtype=np.float64)
     D = X.shape[1]
     theta, var = np.empty((C, D)), np.empty((C, D))
@@ -32,7 +34,7 @@ def gnb_fit(X, codes, C, var_smoothing=1e-9):
     for c in range(C):
         rows = X[codes == c]
         count[c] = len(rows)
-        theta[c], var[c] = seq_mean_var(rows)
+        theta[c], var[c] = seq_mean_var(rows) if len(rows) else (np.nan, np.nan)
     eps = var_smoothing * seq_mean_var(X)[1].max()
     return theta, var + eps, count, eps
 
