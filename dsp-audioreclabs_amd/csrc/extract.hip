@@ -862,10 +862,12 @@ __device__ __forceinline__ void vad_frames_fast(const Ctx &c, const ClipRef &cur
 // sits in the buffer and equal dsp_extract_general's.  Per sample y = w_j x (the reference's
 // windowed frame, :329-331), E += y^2, M += |y|; the weights of a vector's 8 samples are two
 // aligned 16-B reads from the window copy shifted by fs mod 4.  Returns F.
-// vectors per lane in one batch from L2: 7 (896 samples per row) leaves the FAST kernel without
-// VGPR spills; 9 (a whole 1102-sample frame) 2.71 ms, 7 2.65 ms, 6 / 8 2.61-2.64 / 2.66-2.68 ms at
-// 100k clips (profiles/r05s_ab_prefetch_kv.txt, r05kv_ab_r4_batch.txt)
-static constexpr int R4_KV = 7;
+// vectors per lane in one batch from L2: 9 (1152 samples per row), so that a 1102-sample frame is
+// one batch with one exposed L2 round trip; batches of 7 made a second round trip for a lane's
+// last two vectors (2.18 ms against 2.25 at 100k clips, profiles/r4_lockstep_ab.txt).  80 VGPRs,
+// no spill.  Round 5's 9 (2.71 ms against 7's 2.65, profiles/r05s_ab_prefetch_kv.txt,
+// r05kv_ab_r4_batch.txt) came from a build that spilled VGPRs.
+static constexpr int R4_KV = 9;
 // frames of a crop of m = en - st samples (frame_signal, :299-333)
 __device__ __forceinline__ int crop_frame_count(int m, int L, int S) { return (m <= L) ? 1 : (m - L + S - 1) / S + 1; }
 template <bool ZSEG>  // ZCR left to crop_zcr (clip_fast: fE / fM only) or by the row's lanes (clip_body)
@@ -932,8 +934,8 @@ __device__ __forceinline__ int r4_frames(const ExtractParams &p, const Ctx &c, c
                 for (int k = 0; k < KV; k++)
                     if (decltype(ft)::value || 16 * k <= vlim) frame_vec(pt, nt, xv[k], wr, jl + 128 * k, lim, ea, m0, m1);
             };
-            // a batch every lane fills (the first of an unpadded frame) runs without the per-vector
-            // lane bounds
+            // a batch every lane fills (the first of an unpadded frame that spans 16 * KV vectors or
+            // more) runs without the per-vector lane bounds
             const bool full = !padded && __all(vlim >= 16 * (KV - 1));
             if (padded)
                 cx.near0 ? run(BoolT<true>(), BoolT<true>(), BoolT<false>()) : run(BoolT<true>(), BoolT<false>(), BoolT<false>());

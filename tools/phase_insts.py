@@ -3,7 +3,9 @@
 
 Compiles extract.hip with -DDSP_MARKS (region labels ``;@@ NAME`` from MARK() in clip_fast) to
 gfx950 assembly and counts, in layout order from each label to the next, the VALU / SALU / LDS /
-vector-memory instructions and the backward branches (loops, whose bodies run more than once).
+vector-memory instructions, the wait states the compiler inserted (the no-op mnemonic ``s_nop``, a
+column of its own beside the other control instructions) and the backward branches (loops, whose
+bodies run more than once).
 Static counts: straight-line regions (R1, R2) are exact per wave; loop regions (pass A/B, R4)
 are per iteration.
 
@@ -28,7 +30,9 @@ def classify(op):
         return "lds"
     if op.startswith(("buffer_", "global_", "flat_", "scratch_")):
         return "vmem"
-    if op in ("s_waitcnt", "s_nop", "s_barrier", "s_setprio", "s_sleep") or op.startswith("s_cbranch") or \
+    if op == "s_nop":
+        return "s_nop"
+    if op in ("s_waitcnt", "s_barrier", "s_setprio", "s_sleep") or op.startswith("s_cbranch") or \
             op == "s_branch":
         return "ctl"
     if op.startswith("s_"):
@@ -66,7 +70,7 @@ def main():
             tgt = t.split()[-1]
             if labels.get(tgt, 1 << 30) < i:
                 cnt[region]["back_branches"] += 1
-    keys = ("valu", "salu", "lds", "vmem", "ctl", "back_branches")
+    keys = ("valu", "salu", "lds", "vmem", "ctl", "s_nop", "back_branches")
     print("%-10s" % "region" + "".join("%8s" % k[:8] for k in keys))
     tot = collections.Counter()
     for r, c in cnt.items():
