@@ -40,7 +40,8 @@
 //              place.  A frame's emissions are the row of ONE symbol for every lane: NS coalesced loads of
 //              512 contiguous bytes, issued one frame ahead into a second register set (the frame loop is
 //              unrolled by two, so the sets swap without a move; at 32 slots only the upper 16, see
-//              decode_ahead).  The predecessor of slot j is slot j-1
+//              decode_ahead).  The cell sweep, the loads and the minimum are dhmm_cells.h's, which
+//              dhmm_grammar.hip uses too.  The predecessor of slot j is slot j-1
 //              or, at the lane's own j0, the entry (X(t-1), start t): one per-slot select.  The symbols
 //              come 64 frames at a time through the vector path (a lane per frame, the next 64 one chunk
 //              ahead) and a frame's symbol by a readlane: no scalar load in the frame loop.  Transitions:
@@ -55,6 +56,7 @@
 
 #include <algorithm>
 
+#include "dhmm_cells.h"
 #include "dsp_audiorec.h"
 #include "dtw_internal.h"
 #include "hmm_internal.h"
@@ -71,69 +73,16 @@ static bool decode_in_plan(int64_t C, int64_t N, int T, int Smax, int K)
 // dynamic LDS: 16 bytes per frame, then at 32 slots the transitions
 static size_t decode_lds_bytes(int T, int NS) { return (size_t)T * 16 + (NS == 32 ? (size_t)NS * 64 * 16 : 0); }
 
-// a DPP move of both halves of a double; CTRL permutes lanes within a row of 16, every lane has a source
-template <int CTRL>
-__device__ __forceinline__ double decode_dpp(double x)
-{
-    int lo = __double2loint(x), hi = __double2hiint(x);
-    lo = __builtin_amdgcn_update_dpp(lo, lo, CTRL, 0xf, 0xf, false);
-    hi = __builtin_amdgcn_update_dpp(hi, hi, CTRL, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double decode_readlane(double x, int l)
-{
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(x), l), __builtin_amdgcn_readlane(__double2loint(x), l));
-}
-// the smallest of the 64 lanes' values (never NaN), wave-uniform; +0.0 and -0.0 count as equal here and
-// the caller takes the winning lane's own bits
-__device__ __forceinline__ double decode_wave_min(double x)
-{
-    x = dtw_min(x, decode_dpp<0xB1>(x));   // quad_perm [1,0,3,2]
-    x = dtw_min(x, decode_dpp<0x4E>(x));   // quad_perm [2,3,0,1]
-    x = dtw_min(x, decode_dpp<0x141>(x));  // row_half_mirror: the other quad of the 8
-    x = dtw_min(x, decode_dpp<0x140>(x));  // row_mirror: the other 8 of the row
-    const double r0 = decode_readlane(x, 0), r1 = decode_readlane(x, 16), r2 = decode_readlane(x, 32),
-                 r3 = decode_readlane(x, 48);
-    return dtw_min(dtw_min(r0, r1), dtw_min(r2, r3));
-}
-
-// slots whose emissions are asked for one frame ahead: all of them up to 16 slots; at 32 the upper 16, which
-// the descending sweep needs first -- the lower 16 are asked for when the frame starts and arrive behind the
-// upper cells (a second full set of 64 registers would push the cells' operands out of the register file)
-constexpr int decode_ahead(int NS) { return NS == 32 ? 16 : NS; }
-
 #pragma clang fp contract(off)
-// One frame of the NS slots of every lane's model: v, st hold frame t-1 and are replaced by frame t.
-// eh, el: the frame's emissions, the upper slots (asked for a frame ahead) and the lower ones; trr / ltr: (stay, cost of coming in) per slot in registers or, for NS = 32,
-// in LDS at this lane; j0: the lane's entry slot; xprev = X(t-1).  Then the exit: (X, W, B) of frame t
-// to fr[t] by lane 0, X(t) returned.
+// One frame: decode_cells (dhmm_cells.h, its arguments passed on, xprev = X(t-1)), then the exit: (X, W, B) of
+// frame t to fr[t] by lane 0, X(t) returned.
 template <int NS>
 __device__ __forceinline__ double decode_frame(double (&v)[NS], int (&st)[NS], const double (&eh)[decode_ahead(NS)],
                                                const double (&el)[NS - decode_ahead(NS) + 1],
                                                const double2 (&trr)[NS == 32 ? 1 : NS], const double2 *ltr, int j0,
                                                double xprev, int t, int lane, int4 *fr)
 {
-    constexpr int LO = NS - decode_ahead(NS);
-    // at 32 slots the 32 masks (j == j0) would be kept in 64 scalar registers across the frames and spilled
-    // from there; a compare per cell on a value the compiler cannot see through is cheaper
-    if constexpr (NS == 32) asm volatile("" : "+v"(j0));
-    // slots in descending order: slot j reads frame t-1 of slots j and j-1 only, so it is replaced in place
-#pragma unroll
-    for (int j = NS - 1; j >= 0; j--) {
-        double2 sa;
-        if constexpr (NS == 32)
-            sa = ltr[j * 64];
-        else
-            sa = trr[j];
-        const bool ent = j == j0;
-        const double pv = ent ? xprev : (j > 0 ? v[j > 0 ? j - 1 : 0] : (double)INFINITY);
-        const int ps = ent ? t : (j > 0 ? st[j > 0 ? j - 1 : 0] : -1);
-        const double a = v[j] + sa.x;
-        const double b = pv + sa.y;
-        const bool advance = b < a;
-        v[j] = (j >= LO ? eh[j >= LO ? j - LO : 0] : el[j < LO ? j : 0]) + (advance ? b : a);
-        st[j] = advance ? ps : st[j];
-    }
+    decode_cells<NS>(v, st, eh, el, trr, ltr, j0, xprev, t);
     const double ev = v[NS - 1];
     const double m = decode_wave_min(ev);
     const bool any = m < (double)INFINITY;
@@ -145,15 +94,6 @@ __device__ __forceinline__ double decode_frame(double (&v)[NS], int (&st)[NS], c
     return x;
 }
 #pragma clang fp contract(on)
-
-// CNT slots from slot J0 on of symbol k for every lane, the highest first; k is clamped into the table
-template <int NS, int J0, int CNT, int LEN>
-__device__ __forceinline__ void decode_load(double (&e)[LEN], const double *__restrict__ tabl, int k, int K)
-{
-    const double *__restrict__ row = tabl + (size_t)min((unsigned)k, (unsigned)(K - 1)) * (NS * 64);
-#pragma unroll
-    for (int j = CNT - 1; j >= 0; j--) e[j] = row[(J0 + j) * 64];
-}
 
 template <int NS>
 __global__ __launch_bounds__(64) void dhmm_decode(const double *__restrict__ tab, const double2 *__restrict__ tr,

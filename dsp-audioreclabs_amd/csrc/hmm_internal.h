@@ -1,5 +1,6 @@
 // hmm_internal.h -- what the left-to-right HMM files share: hmm.hip (Gaussian), dhmm.hip (discrete, Viterbi),
-// dhmm_fb.hip (discrete, forward-backward), dhmm_decode.hip (connected words) and dhmm_force.hip (forced alignment).
+// dhmm_fb.hip (discrete, forward-backward), dhmm_decode.hip and dhmm_grammar.hip (connected words, free loop and
+// word-pair grammar; their cell sweep is dhmm_cells.h) and dhmm_force.hip (forced alignment).
 //   bounds         of a model set and of a launch, and the discrete plan's dhmm_in_plan
 //   seg rows       hmm_walk_back (the lane's path from the direction words), hmm_seg_ok (a given row's check)
 //   the record     of a discrete model: dhmm_record / dhmm_pitch / dhmm_tr_offset / dhmm_lds_bytes, dhmm_pack

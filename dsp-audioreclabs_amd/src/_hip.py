@@ -43,6 +43,7 @@ EXPORTS = ("dsp_extract_lds_bytes", "dsp_extract_fast_layout", "dsp_extract_feat
            "dsp_vq_workspace_bytes", "dsp_vq_score", "dsp_vq_assign", "dsp_vq_accumulate",
            "dsp_dhmm_workspace_bytes", "dsp_dhmm_score", "dsp_dhmm_align", "dsp_dhmm_accumulate",
            "dsp_dhmm_decode_workspace_bytes", "dsp_dhmm_decode",
+           "dsp_dhmm_decode_grammar_workspace_bytes", "dsp_dhmm_decode_grammar",
            "dsp_dhmm_force_workspace_bytes", "dsp_dhmm_force_align", "dsp_dhmm_force_accumulate",
            "dsp_dhmm_fb_workspace_bytes", "dsp_dhmm_forward", "dsp_dhmm_expect",
            "dsp_pitch_workspace_bytes", "dsp_pitch_track", "dsp_lpc_workspace_bytes", "dsp_lpc_autocorr",
@@ -200,6 +201,12 @@ def load_library(path=LIB_PATH):
         L.dsp_dhmm_decode_workspace_bytes.argtypes = [i64, i64, i32, i32, i32]
         L.dsp_dhmm_decode.restype = i32  # emit, stay, adv, n_states, enter, C, Smax, K, sym, len, N, T, max_words, outputs
         L.dsp_dhmm_decode.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, vp, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]
+    if hasattr(L, "dsp_dhmm_decode_grammar"):  # (older A/B variants lack the word-pair grammar decoder)
+        L.dsp_dhmm_decode_grammar_workspace_bytes.restype = sz
+        L.dsp_dhmm_decode_grammar_workspace_bytes.argtypes = [i64, i64, i32, i32, i32]
+        L.dsp_dhmm_decode_grammar.restype = i32  # the model, enter, pair, leave, C, Smax, K, sym, len, N, T, max_words, outputs
+        L.dsp_dhmm_decode_grammar.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, vp, vp, i64, i32, i32, vp, vp, vp, vp,
+                                              vp, sz, vp]
     if hasattr(L, "dsp_dhmm_force_align"):  # (older A/B variants lack forced alignment and embedded training)
         L.dsp_dhmm_force_workspace_bytes.restype = sz
         L.dsp_dhmm_force_workspace_bytes.argtypes = [i64, i64, i32, i32, i32, i32]

@@ -690,17 +690,27 @@ class DiscreteHmmClassifier(SequenceClassifier):
             raise ValueError("sequence %d has fewer frames than every model has states" % int(np.argmax(label < 0)))
         return self.classes_[label]
 
-    def decode(self, X, lengths=None, word_penalty=0.0, max_words=None):
+    def decode(self, X, lengths=None, word_penalty=0.0, max_words=None, grammar=None):
         """Connected words: each utterance of X is several words in a row with unknown boundaries, decoded by
         the one-pass Viterbi over a loop of the class models (csrc/dhmm_decode.hip, dsp_dhmm_decode, DESIGN.md
         §4.15; at most ``pipeline.DHMM_DECODE_MAX_MODELS`` classes).  The frames are tokenised exactly as
         ``predict`` does.  ``word_penalty``: the cost of starting a word, a scalar or one value per class.
+        ``grammar``: None for the free loop -- any word after any word -- or a ``WordPairGrammar`` over the
+        indices of ``classes_``: the words are then decoded under its costs with the penalty added through
+        ``grammar.plus(word_penalty)`` (csrc/dhmm_grammar.hip, dsp_dhmm_decode_grammar; that
+        call has no ``cum`` output, which this method never returned).
         Returns (labels, starts): per utterance the class labels of its words in time order and their first
         frames, both empty for an utterance no word sequence fits."""
-        from .pipeline import dhmm_decode
+        from .pipeline import dhmm_decode, dhmm_decode_grammar
         Xq, nq = self._symbols(X, lengths)
         sym = self.tokenizer_.transform(self._scale(Xq, nq), nq)
-        _, n_words, words, start, _ = dhmm_decode(self.model_, sym, nq, enter=word_penalty, max_words=max_words)
+        if grammar is None:
+            _, n_words, words, start, _ = dhmm_decode(self.model_, sym, nq, enter=word_penalty, max_words=max_words)
+        else:
+            if grammar.n_classes != len(self.classes_):
+                raise ValueError("the grammar has %d words, the classifier %d classes" % (grammar.n_classes, len(self.classes_)))
+            g = grammar.plus(word_penalty)
+            _, n_words, words, start = dhmm_decode_grammar(self.model_, sym, nq, g.enter, g.pair, g.leave, max_words=max_words)
         n_words, words, start = (t.cpu().numpy() for t in (n_words, words, start))
         kept = np.minimum(n_words, words.shape[1])
         return ([self.classes_[words[i, :kept[i]]] for i in range(len(kept))],
@@ -813,6 +823,79 @@ class DiscreteHmmClassifier(SequenceClassifier):
             self.prob_ = prob
         self._index = None
         return self
+
+
+class WordPairGrammar:
+    """The costs of a word-pair grammar for ``DiscreteHmmClassifier.decode(grammar=...)`` and
+    ``pipeline.dhmm_decode_grammar`` (csrc/dhmm_grammar.hip), host only.  Words are indices
+    into the classifier's ``classes_``.  ``enter`` float64 [C]: the cost of starting an utterance with each
+    word; ``pair`` float64 [C, C]: pair[p, c] the cost of word c following word p; ``leave`` float64 [C]: the
+    cost of ending an utterance on each word.  Finite or +inf; +inf forbids."""
+
+    def __init__(self, enter, pair, leave):
+        self.pair = np.array(pair, np.float64)
+        C = self.pair.shape[0]
+        if self.pair.shape != (C, C) or C < 1:
+            raise ValueError("pair must be [C, C], got shape %s" % (self.pair.shape,))
+        self.enter = np.zeros(C) if enter is None else np.array(np.broadcast_to(np.asarray(enter, np.float64), (C,)))
+        self.leave = np.zeros(C) if leave is None else np.array(np.broadcast_to(np.asarray(leave, np.float64), (C,)))
+        for name in ("enter", "pair", "leave"):
+            v = getattr(self, name)
+            if np.isnan(v).any() or (v == -np.inf).any():
+                raise ValueError("%s must be finite or +inf" % name)
+
+    @property
+    def n_classes(self):
+        return self.pair.shape[0]
+
+    @classmethod
+    def from_transcripts(cls, transcripts, n_classes, alpha=0.5):
+        """Add-alpha bigram estimates with a sentence-end event from word-index sequences (empty ones are
+        skipped): with U utterances, first[c] of them starting with c, n[p, c] bigrams and end[p] utterances
+        ending on p,
+            enter[c]   = -log((first[c] + alpha) / (U + alpha C))
+            pair[p, c] = -log((n[p, c] + alpha) / (sum_c n[p, c] + end[p] + alpha (C + 1)))
+            leave[p]   = -log((end[p]  + alpha) / (sum_c n[p, c] + end[p] + alpha (C + 1)))
+        in fp64 with numpy's logarithm.  With alpha = 0 an unseen event costs +inf."""
+        C, alpha = int(n_classes), np.float64(alpha)
+        if C < 1 or not alpha >= 0:
+            raise ValueError("n_classes >= 1 and alpha >= 0")
+        first, n, end = np.zeros(C), np.zeros((C, C)), np.zeros(C)
+        U = 0
+        for r in transcripts:
+            r = np.asarray(r).astype(np.int64).reshape(-1)
+            if not len(r):
+                continue
+            if r.min() < 0 or r.max() >= C:
+                raise ValueError("a transcript word lies outside [0, %d)" % C)
+            U += 1
+            first[r[0]] += 1
+            end[r[-1]] += 1
+            np.add.at(n, (r[:-1], r[1:]), 1)
+
+        def cost(count, total):
+            num = count + alpha
+            with np.errstate(divide="ignore", invalid="ignore"):
+                return np.where(num > 0, -np.log(num / total), np.inf)
+
+        row = n.sum(axis=1) + end + alpha * np.float64(C + 1)
+        return cls(cost(first, np.float64(U) + alpha * np.float64(C)), cost(n, row[:, None]), cost(end, row))
+
+    @classmethod
+    def from_allowed(cls, follows, first=None, last=None):
+        """A finite-state syntax: ``follows`` bool [C, C] (word c may follow word p), ``first`` / ``last`` bool
+        [C] (may start / end an utterance; None: every word may).  Allowed costs 0.0, forbidden +inf."""
+        follows = np.asarray(follows, bool)
+        C = follows.shape[0]
+        flag = lambda a: np.ones(C, bool) if a is None else np.asarray(a, bool).reshape(C)
+        price = lambda a: np.where(a, 0.0, np.inf)
+        return cls(price(flag(first)), price(follows), price(flag(last)))
+
+    def plus(self, word_penalty):
+        """The grammar with a word penalty (a scalar or one value per word: the cost of starting that word) added
+        to ``enter`` and to every row of ``pair``, in fp64."""
+        pen = np.array(np.broadcast_to(np.asarray(word_penalty, np.float64), (self.n_classes,)))
+        return WordPairGrammar(self.enter + pen, self.pair + pen[None, :], self.leave)
 
 
 def word_error_rate(ref, hyp):

@@ -1171,6 +1171,56 @@ def dhmm_decode(models, sym, lengths, enter=None, max_words=None):
     return score, n_words, words, start, cum
 
 
+def _dhmm_costs(cost, shape, name, device):
+    """A grammar's cost array on the device (float64, finite or +inf), or None."""
+    import torch
+    if cost is None:
+        return None
+    cost = np.ascontiguousarray(np.asarray(_as_host(cost), np.float64))
+    if cost.shape != shape:
+        raise ValueError("%s must have shape %s, got %s" % (name, shape, cost.shape))
+    if np.isnan(cost).any() or (cost == -np.inf).any():
+        raise ValueError("%s must be finite or +inf" % name)
+    return _as_device(cost, torch.float64, device)
+
+
+def dhmm_decode_grammar(models, sym, lengths, enter, pair, leave, max_words=None):
+    """Connected-word decoding under a word-pair grammar (include/dsp_audiorec.h: dsp_dhmm_decode_grammar):
+    ``dhmm_decode``'s one-pass Viterbi with the cost of a word change depending on the word before.  ``enter``
+    float64 [C]: the cost of starting the utterance with each word, None for 0.0; ``pair`` float64 [C, C]:
+    pair[p, c] the cost of word c following word p, any word penalty included; ``leave`` float64 [C]: the cost of
+    ending on each word, None for 0.0; all finite or +inf, +inf forbids.  ``max_words``: the words kept per
+    utterance, T when None.  Returns (score float64 [N], n_words int32 [N], words int32 [N, max_words], start
+    int32 [N, max_words]) on the device; -1 behind an utterance's words.  There is no ``cum``."""
+    import torch
+    d = _hip.require_device()
+    s, n = _dhmm_operand(sym, lengths, d)
+    N, T = s.shape
+    margs = _dhmm_model_args(models, d)
+    C, Smax, K = margs[-3:]
+    if not 1 <= C <= DHMM_DECODE_MAX_MODELS:
+        raise ValueError("a decoding loop takes 1 .. %d word models, got %d" % (DHMM_DECODE_MAX_MODELS, C))
+    if T < 1:
+        raise ValueError(_DHMM_SHAPE)
+    max_words = T if max_words is None else int(max_words)
+    if not 1 <= max_words <= T:
+        raise ValueError("max_words must lie in [1, T = %d]" % T)
+    if pair is None:
+        raise ValueError("a word-pair grammar needs pair [C, C]")
+    costs = [_dhmm_costs(enter, (C,), "enter", d), _dhmm_costs(pair, (C, C), "pair", d), _dhmm_costs(leave, (C,), "leave", d)]
+    score = torch.empty(N, dtype=torch.float64, device=d)
+    n_words = torch.empty(N, dtype=torch.int32, device=d)
+    words = torch.empty((N, max_words), dtype=torch.int32, device=d)
+    start = torch.empty((N, max_words), dtype=torch.int32, device=d)
+    if N > 0:
+        ws = _grown(None, _hip.lib().dsp_dhmm_decode_grammar_workspace_bytes(C, N, T, Smax, K), _DHMM_SHAPE, d)
+        rc = _hip.lib().dsp_dhmm_decode_grammar(*margs[:4], *[_hip.ptr(c) for c in costs], C, Smax, K, _hip.ptr(s), _hip.ptr(n),
+                                                N, T, max_words, _hip.ptr(score), _hip.ptr(n_words), _hip.ptr(words),
+                                                _hip.ptr(start), _hip.ptr(ws), ws.numel(), _hip.stream_handle(d))
+        _hip.check(rc, "dsp_dhmm_decode_grammar")
+    return score, n_words, words, start
+
+
 DHMM_FORCE_MAX_WORDS = 64  # words of one transcript at most (csrc/dhmm_force.hip: a lane per transcript position)
 
 

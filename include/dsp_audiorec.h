@@ -36,7 +36,7 @@ extern "C" {
                               5: queue_ws is 4 KiB (each counter on its own 256-B line);
                               6: the extraction entry points take out_stride (packed result rows);
                                  dsp_knn_classify takes flags (DSP_KNN_REF_READY).
-                              Still 6 with the dsp_mlp_*, dsp_svc_*, dsp_gnb_*, dsp_tree_* and dsp_dtw_* (dsp_dtw_align, dsp_dtw_dba_update included) and dsp_hmm_* and dsp_vq_* and dsp_dhmm_* (dsp_dhmm_decode, dsp_dhmm_forward, dsp_dhmm_expect and dsp_dhmm_force_* included) and dsp_pitch_* and dsp_lpc_* entry points: new symbols only, no
+                              Still 6 with the dsp_mlp_*, dsp_svc_*, dsp_gnb_*, dsp_tree_* and dsp_dtw_* (dsp_dtw_align, dsp_dtw_dba_update included) and dsp_hmm_* and dsp_vq_* and dsp_dhmm_* (dsp_dhmm_decode, dsp_dhmm_decode_grammar, dsp_dhmm_forward, dsp_dhmm_expect and dsp_dhmm_force_* included) and dsp_pitch_* and dsp_lpc_* entry points: new symbols only, no
                               existing signature or meaning changed, so callers built against 6 keep
                               working (a binding that needs them checks for the symbols) */
 
@@ -857,6 +857,50 @@ int dsp_dhmm_decode(const double *emit, const double *stay, const double *adv, c
                     const double *enter, int64_t C, int Smax, int K, const int32_t *sym, const int32_t *len, int64_t N,
                     int T, int max_words, double *score, int32_t *n_words, int32_t *words, int32_t *start, double *cum,
                     void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Connected-word decoding under a word-pair grammar: dsp_dhmm_decode's one-pass Viterbi with the cost of a
+ * word change depending on the word before -- a bigram over the words, or a finite-state syntax ("after
+ * open only door or window") as 0.0 / +inf costs.  csrc/dhmm_grammar.hip, DESIGN.md §4.19.  Bit for bit
+ * like the entry points above: fp64 add and compare only, each operation rounded.
+ *
+ * Inputs.  The model set, sym, len, N, T and max_words are those of dsp_dhmm_decode, with the same value
+ *   rules and bounds: 1 <= C <= 64, Smax <= 32, K <= 256, T <= 1024.
+ *     enter  float64 [C]     the cost of STARTING THE UTTERANCE with word c; NULL means all 0.0
+ *     pair   float64 [C, C]  row-major: pair[p, c] is the cost of word c following word p; required; it
+ *                            carries everything a word change costs, any word penalty included
+ *     leave  float64 [C]     the cost of ending the utterance on word c; NULL means all 0.0
+ *   All three are finite or +inf, never NaN, never -inf; +inf forbids.  A model with n_states outside
+ *   1 .. Smax is neither a predecessor nor a successor and is never read; the cost rows and columns of such
+ *   a model may hold anything.
+ * Recurrence.  The cells are dsp_dhmm_decode's: the value (advance ? b : a) is selected by the same strict
+ *   compare that moves start, and ties stay.  Only the entry term of state 0 changes:
+ *     G(-1, c) = 0.0 + enter[c];   P(-1, c) = -1
+ *     b at s = 0 of frame t:  G(t-1, c)                      (was X(t-1) + enter[c])
+ *     E(t, p) = V(t, p, S_p - 1);   Bx(t, p) = start(t, p, S_p - 1)
+ *     G(t, c) = min over valid p ascending of  E(t, p) + pair[p, c],
+ *               a later p replacing only if strictly smaller;  P(t, c) = that p (-1 when all are +inf)
+ *     score   = min over valid c ascending of  E(n-1, c) + leave[c], same tie rule;  w = that c
+ * Walk back.  Start at t = n-1 with word w.  It starts at b = Bx(t, w).  If b = 0, stop.  Otherwise the
+ *   word before it is P(b-1, w), ending at frame b-1; repeat from there.
+ * Outputs, in time order: score float64 [N], n_words int32 [N] (the true number), words and start int32
+ *   [N, max_words].  The first max_words words are written, with -1 behind them.  The forced rows are
+ *   dsp_dhmm_decode's: score +inf, n_words 0 and -1 rows when n < 1 or n > T, when any sym[t], t < n, lies
+ *   outside [0, K), and when no score is finite.  Any output may be NULL.  There is no cum output: it would
+ *   need every lane's exit value per frame kept as well.
+ * workspace  device scratch of dsp_dhmm_decode_grammar_workspace_bytes(C, N, T, Smax, K) bytes (0: sizes
+ *   outside the plan): dsp_dhmm_decode's transposed set and one 32-bit word per frame and model for each
+ *   utterance in flight.  Nothing in it is carried from one call to the next.
+ * dsp_dhmm_decode_grammar checks its host arguments before any launch (DSP_ERR_ARGS, DSP_ERR_WORKSPACE),
+ * returns DSP_OK with nothing to do (N = 0, every output NULL), makes no host synchronisation and no
+ * allocation, and writes only to its outputs and the workspace, on the caller's stream.
+ */
+size_t dsp_dhmm_decode_grammar_workspace_bytes(int64_t C, int64_t N, int T, int Smax, int K);
+int dsp_dhmm_decode_grammar(const double *emit, const double *stay, const double *adv, const int32_t *n_states,
+                            const double *enter, const double *pair, const double *leave, int64_t C, int Smax, int K,
+                            const int32_t *sym, const int32_t *len, int64_t N, int T, int max_words, double *score,
+                            int32_t *n_words, int32_t *words, int32_t *start, void *workspace, size_t workspace_bytes,
+                            void *stream);
 
 /*
  * Forced alignment and embedded Viterbi re-estimation: an utterance of several words in a row with a KNOWN
